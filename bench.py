@@ -21,6 +21,12 @@ point of the 1/2/4/8-GPU curve is the headline config itself.  Pass
 SRN-shaped batches generated on the device; weights are random-init at the
 full 136.7M-parameter architecture; every timed step is a complete
 forward + backward + gradient all-reduce + Adam update.
+
+A plain run sets up, warms up, times the steps and prints the result line.
+``--full`` adds what takes runs of its own (the gradient-communication record
+``comm`` of a multi-rank run); ``--dump-outputs DIR`` writes what the last timed
+step computed (loss, updated parameters, Adam's first moment; ``--mode sample``:
+the generated views) as ``DIR/<name>.npy`` so that two builds can be compared.
 """
 from __future__ import annotations
 
@@ -100,6 +106,12 @@ def main() -> None:
                     help="cpu: gloo ranks on the host (launcher / plumbing tests)")
     ap.add_argument("--ch", type=int, default=128, help="model width (128 = the benchmarked architecture)")
     ap.add_argument("--emb_ch", type=int, default=1024)
+    ap.add_argument("--full", action="store_true",
+                    help="also run what the headline figure does not need: the gradient-communication "
+                         "diagnostics of a multi-rank run (extra untimed steps after the benchmark) -> `comm`")
+    ap.add_argument("--dump-outputs", dest="dump_outputs", default="", metavar="DIR",
+                    help="after the timed steps, write what the last timed step computed as DIR/<name>.npy "
+                         "(float32; large buffers as a fixed seeded sample)")
     args = ap.parse_args()
     if args.mode == "sample":
         return bench_sample(args)
@@ -139,12 +151,17 @@ def main() -> None:
         graph = ctx.device.type == "cuda" and (mb or local) <= 64
     else:
         graph = bool(int(args.graph))
+    # the trainer opens its metrics file (unused here: log_every 0) under out_dir at construction; the default
+    # is relative to the working directory, which need not be writable for a benchmark run
+    import tempfile
+    scratch = tempfile.TemporaryDirectory(prefix="d3d_bench_")
     cfg = make_config(None, {"model.H": args.imgsize, "model.W": args.imgsize, "data.imgsize": args.imgsize,
                              "model.ch": args.ch, "model.emb_ch": args.emb_ch,
                              "global_batch": global_batch, "micro_batch": mb, "data.synthetic": True,
                              "backend": args.backend, "dtype": args.dtype, "log_every": 0, "ckpt_every": 0,
                              "dist.bucket_mb": args.bucket_mb, "dist.grad_dtype": args.grad_dtype,
-                             "dist.force_comm": bool(args.force_comm), "graph": graph})
+                             "dist.force_comm": bool(args.force_comm), "graph": graph,
+                             "out_dir": scratch.name})
     trainer = Trainer(cfg, ctx)
     data = SyntheticBatches(local, args.imgsize, ctx.device, seed=1234 + ctx.rank)
     pool = [next(data) for _ in range(4)]
@@ -176,7 +193,14 @@ def main() -> None:
     # memory record of the benchmark itself (the comm diagnostics below capture / run extra steps)
     hbm_peak = round(torch.cuda.max_memory_allocated() / 2 ** 30, 2) if ctx.device.type == "cuda" else None
     retries = torch.cuda.memory_stats().get("num_alloc_retries", 0) if ctx.device.type == "cuda" else None
-    comm = comm_diagnostics(trainer, pool, ctx) if (trainer.reducer is not None and trainer.reducer.active) else None
+    if args.dump_outputs and ctx.rank == 0:
+        # what a caller of train_step holds after the last timed step: its loss, the updated parameters
+        # and Adam's first moment (the running average of the gradients)
+        _dump_outputs(args.dump_outputs, {"loss": loss if loss is not None else torch.full((1,), float("nan")),
+                                          "params": trainer.flat.data, "exp_avg": trainer.optim.exp_avg})
+    comm = None
+    if args.full and trainer.reducer is not None and trainer.reducer.active:
+        comm = comm_diagnostics(trainer, pool, ctx)
     if prof is not None:
         prof.__exit__(None, None, None)
         if ctx.rank == 0:
@@ -211,7 +235,7 @@ def main() -> None:
                        "tuned_gemms": bool(getattr(trainer, "tuned_gemms", False)),
                        "backend": "hip" if (ctx.device.type == "cuda" and use_hip(probe)) else "torch"},
             "final_loss": lv,
-            # N > 1: what the gradient communication did (measured after the timed steps)
+            # --full, N > 1: what the gradient communication did (measured after the timed steps)
             "comm": comm,
             "hbm_peak_gib": hbm_peak,
             # caching-allocator retries (a full cache flush + device sync each): non-zero means the step
@@ -223,6 +247,24 @@ def main() -> None:
         }
         print(json.dumps(out), flush=True)
     cleanup()
+
+
+DUMP_SAMPLE = 1 << 22      # elements kept of a larger buffer (16 MiB as float32)
+
+
+def _dump_outputs(dirname: str, tensors: dict) -> None:
+    """``--dump-outputs``: every tensor as ``<dirname>/<name>.npy`` in float32.
+    A buffer of more than DUMP_SAMPLE elements is written as the elements at a
+    fixed set of flat indices (seeded draw on the host: the same positions in
+    every run and every build)."""
+    import numpy as np
+    os.makedirs(dirname, exist_ok=True)
+    for name, t in tensors.items():
+        t = t.detach()
+        if t.numel() > DUMP_SAMPLE:
+            idx = torch.randint(0, t.numel(), (DUMP_SAMPLE,), generator=torch.Generator().manual_seed(0))
+            t = t.reshape(-1)[idx.to(t.device)]
+        np.save(os.path.join(dirname, name + ".npy"), t.float().cpu().numpy().reshape(t.shape or (1,)))
 
 
 def _fallback_count() -> int:
@@ -307,6 +349,8 @@ def bench_sample(args) -> None:
     if dev.type == "cuda":
         torch.cuda.synchronize()
     dt = time.perf_counter() - t0
+    if args.dump_outputs:
+        _dump_outputs(args.dump_outputs, {"sample": out})
 
     res = {"metric": f"{args.timesteps}-step sample wall-clock, stochastic conditioning, bs{b}, {S}x{S}", "value": round(dt, 3),
            "unit": "s", "n_gpus": 1, "steps": args.timesteps, "warmup": args.warmup,

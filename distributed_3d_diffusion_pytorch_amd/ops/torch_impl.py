@@ -327,8 +327,12 @@ def diffusion_inputs(img: torch.Tensor, seed: int, e0: int = 0, cond_prob: float
         torch.arange(HW, device=dev)[None, None, :]
     eps = normal01(s ^ K_EPS, idx).reshape(B, 3, H, W)
     xn = normal01(s ^ K_XN, idx).reshape(B, 3, H, W)
-    alpha = torch.sqrt(torch.sigmoid(lam)).view(B, 1, 1, 1)
-    sigma = torch.sqrt(torch.sigmoid(-lam)).view(B, 1, 1, 1)
+    # alpha / sigma in float64, rounded once: the CPU sigmoid rounds differently in its vector body and its
+    # scalar tail, so in float32 an example's value could move by an ulp with its position in the batch
+    # (seen with 24 vs 64 examples on an AVX-512 host), and the draw must not depend on the split
+    lam64 = lam.double()
+    alpha = torch.sqrt(torch.sigmoid(lam64)).float().view(B, 1, 1, 1)
+    sigma = torch.sqrt(torch.sigmoid(-lam64)).float().view(B, 1, 1, 1)
     x, z = img[:, 0].float(), img[:, 1].float()
     xc = torch.where(keep.view(B, 1, 1, 1), x, xn)
     zt = alpha * z + sigma * eps

@@ -10,8 +10,11 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 
 # several ranks share this host's CPUs: one intra-op pool per rank of the full
-# CPU count oversubscribes it many times over
-torch.set_num_threads(max(1, (os.cpu_count() or 8) // 4))
+# CPU count oversubscribes it many times over.  Sized from torch's own default
+# (which honours OMP_NUM_THREADS), not os.cpu_count(): a job confined to a few
+# CPUs of a many-core host still counts all of them there, and 8 ranks with a
+# quarter of that count each then take minutes over the tiny models here.
+torch.set_num_threads(max(1, min(2, torch.get_num_threads() // 4)))
 
 TINY_OV = {"model.ch": 32, "model.emb_ch": 64, "model.H": 16, "model.W": 16, "data.imgsize": 16,
            "dtype": "fp32", "backend": "torch", "log_every": 0, "ckpt_every": 0, "data.synthetic": True,

@@ -20,7 +20,7 @@ TINY_OV = {"model.ch": 32, "model.emb_ch": 64, "model.H": 16, "model.W": 16, "da
            "data.num_workers": 0, "data.synthetic": True}
 
 
-def _tiny_bench(gpus, extra=(), omp=2):
+def _tiny_bench(gpus, extra=(), omp=2, cwd=ROOT):
     env = dict(os.environ)
     env.pop("WORLD_SIZE", None)
     env.pop("RANK", None)
@@ -28,7 +28,7 @@ def _tiny_bench(gpus, extra=(), omp=2):
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", str(gpus), "--device", "cpu", "--ch", "32",
            "--emb_ch", "64", "--imgsize", "16", "--global_batch", "4", "--steps", "2", "--warmup", "1",
            "--dtype", "fp32", "--backend", "torch", *extra]
-    out = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=300, cwd=ROOT)
+    out = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=300, cwd=cwd)
     assert out.returncode == 0, out.stderr[-3000:]
     lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
     assert len(lines) == 1, out.stdout          # only rank 0 prints
@@ -47,11 +47,11 @@ def test_bench_self_spawns_ranks():
 
 
 def test_bench_reports_comm_diagnostics_four_ranks():
-    """`bench.py --gpus 4`: the JSON carries the gradient-communication record
+    """`bench.py --gpus 4 --full`: the JSON carries the gradient-communication record
     a scaling run needs for diagnosis -- the process group's own world size
     and backend, step path, bucket count / sizes / payload, and the exposed
     all-reduce time per step (max over ranks)."""
-    r = _tiny_bench(4, ("--grad_dtype", "bf16"))
+    r = _tiny_bench(4, ("--grad_dtype", "bf16", "--full"))
     assert r["n_gpus"] == 4
     c = r["comm"]
     assert c["world_pg"] == 4 and c["backend_pg"] == "gloo" and c["active"]
@@ -63,17 +63,40 @@ def test_bench_reports_comm_diagnostics_four_ranks():
 
 def test_bench_eight_ranks_full_node_layout():
     """The 8-GPU launch shape of the scaling run, rehearsed with 8 gloo ranks
-    on the host: `bench.py --gpus 8` self-spawns 8 ranks, the global batch is
+    on the host: `bench.py --gpus 8 --full` self-spawns 8 ranks, the global batch is
     split 8 ways, every rank's process group has world size 8, and the comm
     record carries the bucket layout (sizes summing to the flat gradient, the
     small first bucket first) and an exposed all-reduce time."""
-    r = _tiny_bench(8, ("--global_batch", "8", "--bucket_mb", "0.25"), omp=1)
+    r = _tiny_bench(8, ("--global_batch", "8", "--bucket_mb", "0.25", "--full"), omp=1)
     assert r["n_gpus"] == 8 and r["config"]["parallelism"] == "dp8" and r["config"]["per_gpu_batch"] == 1
     c = r["comm"]
     assert c["world_pg"] == 8 and c["backend_pg"] == "gloo" and c["active"] and "error" not in c, c
     assert c["buckets"] == len(c["bucket_mib"]) >= 2, c
     assert abs(sum(c["bucket_mib"]) - c["total_mib"]) < 0.05
     assert c["exposed_allreduce_ms"] >= 0.0 and r["value"] > 0
+
+
+def test_bench_plain_run_is_lean_and_dumps_outputs(tmp_path):
+    """A plain run takes no comm record (that is `--full`); `--dump-outputs`
+    writes the last timed step's loss, parameters and first moment as float32
+    .npy files, and two runs with the same arguments agree exactly (same
+    inputs, same sample positions).  The run writes nothing else: its working
+    directory (which need not be writable) stays empty."""
+    import numpy as np
+    runs = []
+    cwd = tmp_path / "cwd"
+    cwd.mkdir()
+    for d in ("a", "b"):
+        r = _tiny_bench(1, ("--dump-outputs", str(tmp_path / d)), cwd=str(cwd))
+        assert os.listdir(cwd) == []
+        assert r["comm"] is None and r["steps"] == 2 and r["ms_per_step"] > 0
+        runs.append({n: np.load(tmp_path / d / f"{n}.npy") for n in ("loss", "params", "exp_avg")})
+    a, b = runs
+    assert sorted(os.listdir(tmp_path / "a")) == ["exp_avg.npy", "loss.npy", "params.npy"]
+    for n in a:
+        assert a[n].dtype == np.float32 and np.isfinite(a[n]).all() and np.array_equal(a[n], b[n]), n
+    assert a["loss"].shape == (1,) and a["params"].shape == a["exp_avg"].shape
+    assert np.abs(a["exp_avg"]).max() > 0           # the steps ran: the moment holds gradients
 
 
 def test_bench_launcher_fails_when_a_rank_dies():
@@ -206,7 +229,9 @@ def test_multi_rank_sampling_matches_single_rank(tmp_path):
     root = str(tmp_path / "srn")
     write_synthetic_srn(root, num_instances=1, num_views=3, size=16, seed=2)
     inst = os.path.join(root, sorted(d for d in os.listdir(root) if os.path.isdir(os.path.join(root, d)))[0])
-    env = dict(os.environ, OMP_NUM_THREADS="2")
+    # host ranks on every machine: with a GPU visible sampling.py would put both ranks of the 2-rank run on
+    # device 0 of a one-GPU host, which RCCL refuses
+    env = dict(os.environ, OMP_NUM_THREADS="2", HIP_VISIBLE_DEVICES="", CUDA_VISIBLE_DEVICES="")
     env.pop("WORLD_SIZE", None)
     outs = {}
     for gpus in (1, 2):

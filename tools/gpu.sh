@@ -132,7 +132,7 @@ for step in "$@"; do
         post) gcm=0; gsg=0 ;;
         *) die "fc mode $b" 2 ;;
       esac
-      D3D_GRAPH_COMM=$gcm D3D_GRAPH_SEG=$gsg bench "fc_${b}${c}_b$a" --force_comm --global_batch "$a" \
+      D3D_GRAPH_COMM=$gcm D3D_GRAPH_SEG=$gsg bench "fc_${b}${c}_b$a" --force_comm --full --global_batch "$a" \
         --steps "$(steps_for "$a")" --warmup 4
       python3 -c "import json;d=json.loads(open('$O/fc_${b}${c}_b$a.json').read().strip().splitlines()[-1]);print(d.get('comm'))" ;;
     envfc)                       # envfc:<V=x[+V2=y]>:<bs>:<graph|seg>: fc rehearsal with knobs vs without, interleaved x2
