@@ -55,6 +55,7 @@ class DataConfig:
     num_workers: int = 4
     cache: str = ""                  # preprocessed uint8 cache (.npz dir), "" = PNG path
     seed: int = 0
+    val_path: str = ""               # SRN root whose held-out ("val", 10 %) split scores val_loss; "" = none
 
 
 @dataclass
@@ -113,6 +114,8 @@ class TrainConfig:
     deterministic: bool = False
     profile_steps: str = ""          # e.g. "10-12": torch.profiler window
     graph: bool = False              # capture the step in a HIP graph
+    val_every: int = 0               # log val_loss every this many steps (0 = never)
+    val_batches: int = 8             # batches (of the rank's batch size) one val_loss scores
 
 
 PRESETS: Dict[str, Dict[str, Any]] = {
@@ -184,6 +187,8 @@ def to_dict(cfg: Any) -> Dict[str, Any]:
 
 
 def from_dict(d: Dict[str, Any]) -> TrainConfig:
+    """Fields the dict lacks (a checkpoint written before they existed) keep
+    their defaults; keys that are no field any more are ignored."""
     cfg = TrainConfig()
     flat: Dict[str, Any] = {}
 

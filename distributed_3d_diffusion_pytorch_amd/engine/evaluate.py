@@ -1,0 +1,186 @@
+"""Evaluation: novel-view synthesis scored against ground truth (the 3DiM
+protocol) and the held-out training loss.
+
+For every held-out object one input view is given and the listed target views
+are generated -- with ``autoregressive`` each generated view joins the object's
+record (stochastic conditioning), otherwise every view is generated from the
+input view alone.  Up to ``batch`` objects run as ONE graph-replayed sampler
+step (:meth:`DiffusionSampler.sample_groups`: one chain per (object, guidance
+weight), the conditioning computed once per object and class), and the results
+are scored on the device by ``ops.image_metrics(quantize=True)``, i.e. exactly
+as the PNGs a writer would store.  Single process.
+"""
+from __future__ import annotations
+
+import math
+import os
+from typing import Callable, Dict, Iterable, List, Optional, Sequence
+
+import torch
+
+from .. import ops
+from .sampler import DiffusionSampler, RecordEntry
+
+_VAL_KEY = 0x76616C6964617465      # "validate": keeps the validation draw apart from every training step's
+_M64 = (1 << 64) - 1
+
+
+# ------------------------------------------------------------ held-out loss
+def validation_seed(seed: int, i: int) -> int:
+    """RNG seed of validation batch ``i``: a function of (seed, the validation
+    constant, i) only, so every call scores the same (t, eps, CFG-drop) draw."""
+    base = (int(seed) * 0x2545F4914F6CDD1D + _VAL_KEY) & _M64
+    return (base + (i + 1) * 0x9E3779B97F4A7C15) & _M64
+
+
+@torch.no_grad()
+def heldout_loss(model, batches: Iterable, seed: int, diffusion_cfg, dtype) -> torch.Tensor:
+    """Mean training loss (``ops.diffusion_inputs`` -> forward ->
+    ``ops.diff_loss_nhwc``) of ``model`` in eval mode over ``batches`` of
+    (img [B,2,3,H,W], R, T, K) on the model's device, batch i drawn with
+    ``validation_seed(seed, i)``.  Returns a device scalar; the model's
+    train / eval mode is restored, nothing else is touched."""
+    dc = diffusion_cfg
+    was_training = model.training
+    model.eval()
+    total, n = None, 0
+    try:
+        for i, (img, R, T, K) in enumerate(batches):
+            xz, eps, logsnr, keep = ops.diffusion_inputs(img, validation_seed(seed, i), 0, dc.cond_prob,
+                                                         dc.logsnr_min, dc.logsnr_max, dtype)
+            y = model({"xz": xz, "logsnr": logsnr, "R": R, "t": T, "K": K}, cond_mask=keep, head_nhwc=True)
+            loss = ops.diff_loss_nhwc(y, eps, dc.loss_type).detach().float()
+            total = loss if total is None else total + loss
+            n += 1
+    finally:
+        if was_training:
+            model.train()
+    if n == 0:
+        raise ValueError("the held-out loss needs at least one batch")
+    return total / n
+
+
+# ------------------------------------------------------------------ objects
+class EvalObject:
+    """One object: ``imgs[v]`` [3,H,W] fp32 in [-1, 1], ``R[v]`` [3,3], ``T[v]``
+    [3] for the views v the evaluation touches, and its intrinsics K [3,3]."""
+
+    def __init__(self, name: str, imgs: Dict[int, torch.Tensor], R: Dict[int, torch.Tensor],
+                 T: Dict[int, torch.Tensor], K: torch.Tensor):
+        self.name, self.imgs, self.R, self.T, self.K = name, imgs, R, T, K
+
+
+def load_objects(root: str, index: str = "", split: str = "val", instances: int = 0, imgsize: int = 64,
+                 views: Sequence[int] = (0, 1)) -> List[EvalObject]:
+    """The first ``instances`` (0 = all) objects of ``split`` under the SRN
+    root -- the 90 / 10 split rule of :class:`SRNDataset` -- with the listed
+    views (positions in the object's sorted view list)."""
+    from ..data.srn import load_image, load_index, read_matrix, scan_index, split_ids
+    idx = load_index(index) if index and os.path.exists(index) else scan_index(root)
+    ids = split_ids(list(idx.keys()), split)
+    if instances:
+        ids = ids[:instances]
+    out = []
+    f32 = lambda a: torch.tensor(a, dtype=torch.float32)  # noqa: E731
+    for inst in ids:
+        names = sorted(idx[inst])
+        if max(views) >= len(names):
+            raise ValueError(f"{inst} has {len(names)} views, view {max(views)} requested")
+        imgs, Rs, Ts = {}, {}, {}
+        for v in views:
+            stem = names[v][:-4]
+            imgs[v] = f32(load_image(os.path.join(root, inst, "rgb", names[v]), imgsize))
+            pose = read_matrix(os.path.join(root, inst, "pose", stem + ".txt"), (4, 4))
+            Rs[v], Ts[v] = f32(pose[:3, :3]), f32(pose[:3, 3])
+        K = read_matrix(os.path.join(root, inst, "intrinsics", names[0][:-4] + ".txt"), (3, 3))
+        out.append(EvalObject(inst, imgs, Rs, Ts, f32(K)))
+    return out
+
+
+# --------------------------------------------------------------- evaluation
+@torch.no_grad()
+def evaluate_objects(model, objects: Sequence[EvalObject], input_view: int = 0, views: Sequence[int] = (1,),
+                     w: Sequence[float] = (3.0,), timesteps: int = 256, batch: int = 64,
+                     autoregressive: bool = False, seed: int = 0, device=None, ref_quirk: bool = False,
+                     graph: Optional[bool] = None, keep_images: bool = False,
+                     on_view: Optional[Callable] = None):
+    """Generate ``views`` of every object from its ``input_view`` and score
+    them.  Returns ``(rows, images)``: one row ``{instance, view, w, chain,
+    mse, psnr, ssim}`` per (object, view, w) -- ``chain`` the global chain
+    index, ``psnr`` None where the images are identical (mse == 0) -- and,
+    with ``keep_images``, ``images[(instance, view)]`` = the generated
+    [len(w),3,H,W] batch on the CPU.  ``on_view(objects, view, out, gt)`` is
+    called with each generated batch ([G * len(w),3,H,W], object-major) and
+    its ground truth [G,3,H,W]."""
+    dev = torch.device(device) if device is not None else next(model.parameters()).device
+    nw = len(w)
+    rows: List[dict] = []
+    images: Dict[tuple, torch.Tensor] = {}
+    for s in range(0, len(objects), max(int(batch), 1)):
+        objs = objects[s:s + max(int(batch), 1)]
+        G = len(objs)
+        # chains are object-major and numbered globally, so a row (and its noise) does not depend on `batch`
+        smp = DiffusionSampler(model, timesteps, ref_quirk, seed=seed, device=dev, chain_offset=s * nw, graph=graph)
+        group = torch.arange(G).repeat_interleave(nw)
+        wv = torch.tensor([float(x) for x in w]).repeat(G)
+        K = torch.stack([o.K for o in objs]).to(dev)
+        records = [[RecordEntry(o.imgs[input_view].to(dev)[None].expand(nw, -1, -1, -1).contiguous(),
+                                o.R[input_view].to(dev), o.T[input_view].to(dev))] for o in objs]
+        for v in views:
+            tR = torch.stack([o.R[v] for o in objs]).to(dev)
+            tT = torch.stack([o.T[v] for o in objs]).to(dev)
+            out = smp.sample_groups(records, tR, tT, K, wv, group).float()
+            gt = torch.stack([o.imgs[v] for o in objs]).to(dev)
+            mse, ssim = ops.image_metrics(out, gt.repeat_interleave(nw, 0), quantize=True)
+            mse_l, ssim_l = mse.double().cpu().tolist(), ssim.double().cpu().tolist()
+            for gi, o in enumerate(objs):
+                for i in range(nw):
+                    j = gi * nw + i
+                    rows.append({"instance": o.name, "view": int(v), "w": float(w[i]), "chain": s * nw + j,
+                                 "mse": mse_l[j], "psnr": 10.0 * math.log10(1.0 / mse_l[j]) if mse_l[j] > 0 else None,
+                                 "ssim": ssim_l[j]})
+                if keep_images:
+                    images[(o.name, int(v))] = out[gi * nw:(gi + 1) * nw].cpu()
+                if autoregressive:
+                    records[gi].append(RecordEntry(out[gi * nw:(gi + 1) * nw].contiguous(), o.R[v].to(dev),
+                                                   o.T[v].to(dev)))
+            if on_view is not None:
+                on_view(objs, int(v), out, gt)
+    return rows, images
+
+
+def summarize(rows: Sequence[dict]) -> dict:
+    """Per guidance weight: ``psnr_mean`` over the images with mse > 0 (the
+    rest are counted in ``n_identical``; their PSNR is infinite) and
+    ``ssim_mean`` over all images."""
+    out = {"n_images": len(rows), "n_identical": sum(1 for r in rows if not r["mse"] > 0), "psnr_mean": {},
+           "ssim_mean": {}}
+    for wv in sorted({r["w"] for r in rows}):
+        sel = [r for r in rows if r["w"] == wv]
+        ps = [r["psnr"] for r in sel if r["mse"] > 0]
+        out["psnr_mean"][f"{wv:g}"] = sum(ps) / len(ps) if ps else None
+        out["ssim_mean"][f"{wv:g}"] = sum(r["ssim"] for r in sel) / len(sel)
+    return out
+
+
+# ------------------------------------------------------------------ loading
+def load_model(path: str, imgsize: int, device, ema: bool = False):
+    """The model of a checkpoint, as ``sampling.py`` loads it: our checkpoints
+    carry their config, reference checkpoints (with or without ``module.``)
+    are ``XUNet(H, W, ch=128)``.  Returns (model in eval mode, TrainConfig or None)."""
+    from ..models import XUNet
+    from ..utils import load_checkpoint, load_model_weights
+    dev = torch.device(device)
+    ck = load_checkpoint(path)
+    cfg = None
+    if isinstance(ck.get("config"), dict):
+        from ..config import from_dict
+        cfg = from_dict(ck["config"])
+        cfg.model.H = cfg.model.W = imgsize
+        model = XUNet(cfg.model).to(dev)
+    else:
+        model = XUNet(H=imgsize, W=imgsize, ch=128).to(dev)
+    load_model_weights(model, ck.get("ema") if (ema and ck.get("ema")) else ck["model"])
+    model.compute_dtype = torch.bfloat16 if dev.type == "cuda" else torch.float32
+    model.eval()
+    return model, cfg

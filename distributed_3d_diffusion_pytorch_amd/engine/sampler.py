@@ -25,6 +25,10 @@ Differences by design (same math, §2.5 of SURVEY):
   shared by the GN-FiLM kernels through a row -> class map
   (``XUNet.forward(shared_cond=)``; ``share_cond=False`` restores the
   per-example forward);
+* :meth:`DiffusionSampler.sample_groups` batches chains of DIFFERENT objects
+  (each group of chains with its own record and target pose) into the same
+  single step: the conditioning is computed for the 2G classes (cond / uncond
+  per group) and read through the same row -> class map;
 * D9 (noise skipped at t=0.5 where logsnr_next == 0) is opt-in via
   ``ref_quirk``; default adds noise on every step but the last.
 """
@@ -72,6 +76,7 @@ class DiffusionSampler:
         self.lam0 = float(logsnr_schedule_cosine(torch.zeros(()), logsnr_min=logsnr_min, logsnr_max=logsnr_max))
         self.graph = graph
         self._g = None
+        self._gg = None                 # the graphed step of sample_groups
 
     # ------------------------------------------------------------ scalars
     def step_seed(self, k: int) -> int:
@@ -123,13 +128,28 @@ class DiffusionSampler:
                 "example_class": torch.cat([torch.zeros(b, dtype=torch.int32, device=dev),
                                             torch.ones(b, dtype=torch.int32, device=dev)])}
 
+    @staticmethod
+    def group_cond(Rg, Tg, Kg, logsnr: torch.Tensor, group: torch.Tensor) -> dict:
+        """The 2G distinct conditioning examples of a CFG batch whose b chains
+        belong to G groups with one pose pair each: class g conditional for
+        group g, class G + g its unconditional twin.  Rg [G,2,3,3], Tg [G,2,3],
+        Kg [G,3,3], logsnr [2G,2] (any 2G of the batch's identical [lambda0,
+        lambda] rows), group int [b]."""
+        dev = Rg.device
+        G = Rg.shape[0]
+        grp = group.to(device=dev, dtype=torch.int32)
+        ones = torch.ones(G, dtype=torch.bool, device=dev)
+        return {"R": torch.cat([Rg, Rg]), "t": torch.cat([Tg, Tg]), "K": torch.cat([Kg, Kg]), "logsnr": logsnr,
+                "cond_mask": torch.cat([ones, ~ones]), "example_class": torch.cat([grp, grp + G])}
+
     # ------------------------------------------------------- eager step
     @torch.no_grad()
-    def denoise_eps(self, x_cond, z, R, T, K, logsnr: float, k: int = 0, shared: bool = False):
+    def denoise_eps(self, x_cond, z, R, T, K, logsnr: float, k: int = 0, shared: bool = False, group=None):
         """CFG pair in one forward: rows [0,b) conditional, [b,2b) unconditional
         (x replaced by the step-k counter-based noise, rays zeroed via
         cond_mask=False).  ``shared``: R/T/K are the same for every chain
-        (as in :meth:`sample`): condition once per class."""
+        (as in :meth:`sample`): condition once per class.  ``group`` (int [b]):
+        R/T/K are per GROUP ([G,...]) and chain j reads group[j]'s."""
         from ..ops import torch_impl as TI
         b = z.shape[0]
         dev = z.device
@@ -137,7 +157,10 @@ class DiffusionSampler:
         lam = torch.full((2 * b,), float(logsnr), device=dev)
         logsnr2 = torch.stack([torch.full_like(lam, self.lam0), lam], 1)
         batch = {"x": torch.cat([x_cond, x_unc]), "z": torch.cat([z, z])}
-        if shared:
+        if group is not None:
+            sc = self.group_cond(R, T, K, logsnr2[:2 * R.shape[0]], group)
+            eps = self.model(batch, shared_cond=sc).float()
+        elif shared:
             eps = self.model(batch, shared_cond=self.shared_cond(R[0], T[0], K[0], logsnr2[:2], b)).float()
         else:
             batch.update({"logsnr": logsnr2, "R": torch.cat([R, R]), "t": torch.cat([T, T]),
@@ -148,20 +171,34 @@ class DiffusionSampler:
         return eps[:b], eps[b:]
 
     @torch.no_grad()
-    def step(self, z, x_cond, R, T, K, w, k: int, shared: bool = False):
+    def step(self, z, x_cond, R, T, K, w, k: int, shared: bool = False, group=None):
         """One ancestral CFG step for b chains.  ``shared``: every chain has
-        the same R/T/K (conditioning computed once per class)."""
+        the same R/T/K (conditioning computed once per class).  ``group``
+        (int [b], values in [0, G)): R [G,2,3,3], T [G,2,3] and K [G,3,3] are
+        per group and chain j is conditioned on group[j]'s (conditioning
+        computed once per group and class)."""
         from ..ops import torch_impl as TI
+        if group is not None:
+            self._check_group(group, z.shape[0], R.shape[0])
         if self._hip(z):
-            return self._hip_step(z, x_cond, R, T, K, w, k, shared)
-        eps_c, eps_u = self.denoise_eps(x_cond, z, R, T, K, self.lam[k], k, shared)
+            return self._hip_step(z, x_cond, R, T, K, w, k, shared, group)
+        eps_c, eps_u = self.denoise_eps(x_cond, z, R, T, K, self.lam[k], k, shared, group)
         mean, var = cfg_posterior(z, eps_c, eps_u, w, torch.tensor(self.lam[k]), torch.tensor(self.lam_next[k]))
         if not self.add_noise(k):
             return mean
         return mean + var.sqrt() * self._noise(TI.K_NZ, k, tuple(z.shape), z.device)
 
+    @staticmethod
+    def _check_group(group, b: int, G: int) -> List[int]:
+        """The chain -> group map as a list; every group needs a chain (the
+        2G conditioning classes read 2G of the batch's 2b logSNR rows)."""
+        grp = [int(v) for v in group.tolist()]
+        if len(grp) != b or sorted(set(grp)) != list(range(G)):
+            raise ValueError(f"group must map {b} chains onto all of the {G} groups, got {grp}")
+        return grp
+
     @torch.no_grad()
-    def _hip_step(self, z, x_cond, R, T, K, w, k, shared=False):
+    def _hip_step(self, z, x_cond, R, T, K, w, k, shared=False, group=None):
         """Eager form of the graphed step (same kernels, host seed)."""
         from ..ops import hip_impl
         b, _, H, W = z.shape
@@ -171,7 +208,10 @@ class DiffusionSampler:
         logsnr = torch.empty(2 * b, 2, dtype=torch.float32, device=dev)
         z = z.float().contiguous().clone()
         hip_impl.sampler_inputs(x_cond.float().contiguous(), z, prm, None, self.step_seed(k), self.c0, xz, logsnr)
-        if shared:
+        if group is not None:
+            sc = self.group_cond(R.float(), T.float(), K.float(), logsnr[:2 * R.shape[0]], group)
+            y = self.model({"xz": xz}, shared_cond=sc, head_nhwc=True)
+        elif shared:
             sc = self.shared_cond(R[0].float(), T[0].float(), K[0].float(), logsnr[:2], b)
             y = self.model({"xz": xz}, shared_cond=sc, head_nhwc=True)
         else:
@@ -220,6 +260,14 @@ class DiffusionSampler:
                 y = self.model(batch, cond_mask=g["mask"], head_nhwc=True)
             hip_impl.sampler_step2(g["z"], y, g["w"], g["prm"], g["sd"], self.seed_base, self.c0)
 
+        self._g = self._capture(g, body)
+        return g
+
+    def _capture(self, g: dict, body) -> dict:
+        """Warm ``body`` up on a side stream, capture it into ``g["graph"]``
+        and restore ``g["z"]`` (the step updates it in place)."""
+        from ..ops import hip_impl
+        dev = self.device
         z_keep = g["z"].clone()
         s = torch.cuda.Stream(device=dev)
         s.wait_stream(torch.cuda.current_stream(dev))
@@ -237,8 +285,44 @@ class DiffusionSampler:
         g["z"].copy_(z_keep)
         g["graph"] = graph
         g["weights"] = self._weight_signature()
-        self._g = g
         return g
+
+    def _group_graph_setup(self, b: int, G: int, H: int, W: int, grp: List[int], K: torch.Tensor, w: torch.Tensor):
+        """The graphed step of :meth:`sample_groups`: static pose buffers
+        [2, G, 2, 3, 3] / [2, G, 2, 3] (cond classes, then their unconditional
+        twins; frame 0 = record view, frame 1 = target view), filled before
+        each replay; cached on (b, G, H, W, group map, K, w)."""
+        from ..ops import hip_impl
+        dev = self.device
+        g = {"key": (b, G, H, W, tuple(grp)), "K": K.clone(), "w": w.clone()}
+        g["xc"] = torch.zeros(b, 3, H, W, device=dev)
+        g["z"] = torch.zeros(b, 3, H, W, device=dev)
+        g["R"] = torch.zeros(2, G, 2, 3, 3, device=dev)
+        g["t"] = torch.zeros(2, G, 2, 3, device=dev)
+        g["prm_table"] = torch.tensor([self.params(k) for k in range(self.T)], dtype=torch.float32).to(dev)
+        g["prm"] = g["prm_table"][0].clone()
+        g["sd"] = torch.zeros(3, dtype=torch.int64, device=dev)
+        g["xz"] = torch.empty(4 * b, H, W, 8, dtype=torch.bfloat16, device=dev)
+        g["logsnr"] = torch.empty(2 * b, 2, dtype=torch.float32, device=dev)
+        ones = torch.ones(G, dtype=torch.bool, device=dev)
+        cls = torch.tensor(grp, dtype=torch.int32, device=dev)
+        g["sc"] = {"R": g["R"].view(2 * G, 2, 3, 3), "t": g["t"].view(2 * G, 2, 3), "K": torch.cat([K, K]),
+                   "logsnr": g["logsnr"][:2 * G], "cond_mask": torch.cat([ones, ~ones]),
+                   "example_class": torch.cat([cls, cls + G])}
+
+        def body():
+            hip_impl.sampler_inputs(g["xc"], g["z"], g["prm"], g["sd"], self.seed_base, self.c0, g["xz"],
+                                    g["logsnr"])
+            y = self.model({"xz": g["xz"]}, shared_cond=g["sc"], head_nhwc=True)
+            hip_impl.sampler_step2(g["z"], y, g["w"], g["prm"], g["sd"], self.seed_base, self.c0)
+
+        self._gg = self._capture(g, body)
+        return g
+
+    def _group_graph_ok(self, b, G, H, W, grp, K, w) -> bool:
+        g = self._gg
+        return bool(g is not None and g["key"] == (b, G, H, W, tuple(grp)) and
+                    g["weights"] == self._weight_signature() and torch.equal(g["K"], K) and torch.equal(g["w"], w))
 
     def _weight_signature(self):
         """The captured graph reads the cached bf16 weight operands by address:
@@ -303,6 +387,90 @@ class DiffusionSampler:
                 R = torch.stack([e.R.to(dev), target_R.to(dev)], 0)[None].expand(b, 2, 3, 3).contiguous()
                 T = torch.stack([e.T.to(dev), target_T.to(dev)], 0)[None].expand(b, 2, 3).contiguous()
                 z = self.step(z, e.img.to(dev), R, T, Kb, w, k, shared=self.share_cond)
+        if model_was_training:
+            self.model.train()
+        return z
+
+    # ---------------------------------------------------- sample_groups
+    @torch.no_grad()
+    def sample_groups(self, records: List[List[RecordEntry]], target_R: torch.Tensor, target_T: torch.Tensor,
+                      K: torch.Tensor, w: torch.Tensor, group, progress: bool = False) -> torch.Tensor:
+        """:meth:`sample` for b chains of G different objects in ONE step per
+        timestep.  ``group`` (int [b], every value of [0, G) present) maps
+        chain j to its group; group g has its own record ``records[g]`` --
+        entries with images [b_g,3,H,W] for the chains of that group in chain
+        order and the view's R / T -- and its own target pose ``target_R[g]``
+        [G,3,3], ``target_T[g]`` [G,3]; ``K`` is [3,3] or [G,3,3], ``w`` [b].
+
+        All records have the same length and every step draws ONE record index
+        for all groups -- the single ``choice_rng`` draw per step that
+        :meth:`sample` consumes -- so the chains of group g equal a
+        :meth:`sample` run of object g alone with the same seed and
+        ``chain_offset`` (noise is keyed by the global chain index
+        ``chain_offset + j``), and the step stays one graph.  With
+        ``share_cond=False`` the conditioning is computed per chain through
+        the eager step."""
+        from ..ops import torch_impl as TI
+        dev = self.device
+        w = w.to(dev).float().contiguous()
+        b, G = w.shape[0], len(records)
+        grp = self._check_group(torch.as_tensor(group), b, G)
+        L = len(records[0])
+        if L == 0 or any(len(r) != L for r in records):
+            raise ValueError(f"sample_groups needs non-empty records of one length, got {[len(r) for r in records]}")
+        H, W = records[0][0].img.shape[-2:]
+        members = [torch.tensor([j for j in range(b) if grp[j] == g_], device=dev) for g_ in range(G)]
+        for g_ in range(G):
+            for e in records[g_]:
+                if tuple(e.img.shape) != (len(members[g_]), 3, H, W):
+                    raise ValueError(f"group {g_}: record images {tuple(e.img.shape)} for {len(members[g_])} chains "
+                                     f"at {H}x{W}")
+        tR = target_R.to(dev).float().reshape(G, 3, 3)
+        tT = target_T.to(dev).float().reshape(G, 3)
+        Kg = K.to(dev).float()
+        Kg = (Kg.reshape(1, 3, 3).expand(G, 3, 3) if Kg.dim() == 2 else Kg.reshape(G, 3, 3)).contiguous()
+        # per record index: the b conditioning images in chain order and the G pose pairs
+        xcs, Rs, Ts = [], [], []
+        for i in range(L):
+            xc = torch.empty(b, 3, H, W, device=dev)
+            for g_ in range(G):
+                xc[members[g_]] = records[g_][i].img.to(dev).float()
+            xcs.append(xc)
+            Rs.append(torch.stack([torch.stack([records[g_][i].R.to(dev).float() for g_ in range(G)]), tR], 1))
+            Ts.append(torch.stack([torch.stack([records[g_][i].T.to(dev).float() for g_ in range(G)]), tT], 1))
+        group_t = torch.tensor(grp, dtype=torch.int32, device=dev)
+
+        model_was_training = self.model.training
+        self.model.eval()
+        z = self._noise(TI.K_Z0, None, (b, 3, H, W), dev)
+        it = range(self.T)
+        if progress:
+            try:
+                from tqdm import tqdm
+                it = tqdm(it, desc="diffusion", leave=False)
+            except Exception:
+                pass
+        if self._hip(z) and (self.graph is None or self.graph) and self.share_cond:
+            if not self._group_graph_ok(b, G, H, W, grp, Kg, w):
+                self._group_graph_setup(b, G, H, W, grp, Kg, w)
+            g = self._gg
+            g["z"].copy_(z)
+            for k in it:
+                i = self.choice_rng.randrange(L)
+                g["xc"].copy_(xcs[i])
+                g["R"].copy_(Rs[i][None].expand(2, G, 2, 3, 3))
+                g["t"].copy_(Ts[i][None].expand(2, G, 2, 3))
+                g["prm"].copy_(g["prm_table"][k])
+                g["sd"][0].fill_(k + 1)
+                g["graph"].replay()
+            z = g["z"].clone()
+        else:
+            for k in it:
+                i = self.choice_rng.randrange(L)
+                if self.share_cond:
+                    z = self.step(z, xcs[i], Rs[i], Ts[i], Kg, w, k, group=group_t)
+                else:
+                    z = self.step(z, xcs[i], Rs[i][group_t.long()], Ts[i][group_t.long()], Kg[group_t.long()], w, k)
         if model_was_training:
             self.model.train()
         return z

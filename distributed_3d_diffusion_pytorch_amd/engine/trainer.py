@@ -331,6 +331,48 @@ class Trainer:
         return loss
 
     # ------------------------------------------------------------------
+    @torch.no_grad()
+    def validation_loss(self, batches) -> float:
+        """Mean training loss (``ops.diffusion_inputs`` -> forward ->
+        ``ops.diff_loss_nhwc``) over ``batches`` of (img, R, T, K), in eval
+        mode.  The draw of batch i is seeded by (cfg.seed, a validation
+        constant, i) only -- not by the step or the rank -- so every call
+        scores the same (t, eps, CFG-drop) draw and the values of different
+        steps are comparable.  Averaged over ranks.  Reads the parameters
+        only: the optimizer, the step counter, the RNG states, the dropout
+        seed word and the gradient buffers stay as they are."""
+        from .evaluate import heldout_loss
+        self.sync()                         # the graph step may still hold the last update
+        mean = heldout_loss(self.model, (self._to_dev(b) for b in batches), self.cfg.seed, self.cfg.diffusion,
+                            self.dtype)
+        if self.ctx.world > 1:
+            import torch.distributed as dist
+            dist.all_reduce(mean)
+            mean = mean / self.ctx.world
+        return float(mean)
+
+    def make_val_data(self) -> list:
+        """The fixed validation batches of this rank (``cfg.val_batches`` of
+        the rank's batch size, materialised once): synthetic batches with a
+        seed of their own, or the first held-out examples of ``data.val_path``."""
+        dc = self.cfg.data
+        nb = max(int(self.cfg.val_batches), 1)
+        if dc.synthetic:
+            from ..data import SyntheticBatches
+            it = SyntheticBatches(self.local_batch, dc.imgsize, self.device,
+                                  seed=dc.seed * 7919 + self.ctx.rank + 104729)
+            return [next(it) for _ in range(nb)]
+        if not dc.val_path:
+            raise ValueError("val_every > 0 needs data.val_path (train.py --val_data) or synthetic data")
+        from ..data import SRNDataset, ShardSampler, collate
+        index =dc.index if os.path.abspath(dc.val_path) == os.path.abspath(dc.path) else ""
+        ds = SRNDataset("val", dc.val_path, index, dc.imgsize, seed=dc.seed)
+        if len(ds) == 0:
+            raise ValueError(f"no held-out instances under {dc.val_path}")
+        mine = list(ShardSampler(len(ds), self.ctx.rank, self.ctx.world, shuffle=False))[: nb * self.local_batch]
+        return [self._to_dev(collate([ds[i] for i in mine[s:s + self.local_batch]]))
+                for s in range(0, len(mine), self.local_batch)]
+
     def make_data(self) -> Tuple[Iterator, Optional[object], Optional[object]]:
         dc = self.cfg.data
         if dc.synthetic:
@@ -367,6 +409,7 @@ class Trainer:
         timer.start()
         last = {}
         done = False
+        val_data = self.make_val_data() if cfg.val_every > 0 else None
         for epoch in range(self.epoch, cfg.num_epochs):
             self.epoch = epoch
             n = self.epoch_pos                # > 0 only for the epoch a mid-epoch checkpoint resumes
@@ -407,6 +450,13 @@ class Trainer:
                               f"{rep['tflops']:.1f} TFLOP/s", flush=True)
                         self.logger.log(**last)
                     timer.start()
+                if val_data is not None and self.step % cfg.val_every == 0:
+                    t_val = time.perf_counter()
+                    vl = self.validation_loss(val_data)
+                    if self.ctx.is_main:
+                        print(f"[step {self.step}] val_loss {vl:.5f}", flush=True)
+                        self.logger.log(step=self.step, epoch=epoch, val_loss=vl)
+                    timer.t0 += time.perf_counter() - t_val     # keep the pass out of the throughput figures
                 if cfg.ckpt_every and self.step % cfg.ckpt_every == 0:
                     self.save("after_warmup.pt", epoch_pos=n)
                 if cfg.max_steps and self.step >= cfg.max_steps:

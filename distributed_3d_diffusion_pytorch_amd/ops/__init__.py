@@ -188,13 +188,35 @@ def ray_posenc(R, t, K, H: int, W: int, cond_mask, pos_emb, first_emb, other_emb
                          rescale_from).to(out_dtype)
 
 
+def image_metrics(pred, target, quantize: bool = True):
+    """Per-image ``(mse [N], ssim [N])`` (fp32) of two ``[N, C, H, W]`` batches
+    in [-1, 1], scored on the [0, 1] scale.  ``quantize``: both images first
+    go through the uint8 value ``sampling.py:save_png`` writes, so the result
+    equals the metrics of the written PNGs.  SSIM is Wang et al. 2004 (11-tap
+    Gaussian, sigma 1.5, valid region, L = 1, per channel).  HIP
+    (``csrc/metrics.hip``) on the GPU, the float64 torch composition on the CPU."""
+    if pred.dim() != 4 or pred.shape != target.shape:
+        raise ValueError(f"image_metrics takes two [N,C,H,W] batches of one shape, got {tuple(pred.shape)} and "
+                         f"{tuple(target.shape)}")
+    if pred.shape[-2] < 11 or pred.shape[-1] < 11:
+        raise ValueError(f"image_metrics needs H, W >= 11 (one SSIM window), got {tuple(pred.shape[-2:])}")
+    if pred.is_cuda and pred.shape[0] > 0 and use_hip(pred, any_dtype=True):
+        return _h().image_metrics(pred, target, quantize)
+    return _t.image_metrics(pred, target, quantize)
+
+
+def psnr(mse):
+    """``10 log10(1 / mse)`` on the [0, 1] scale; ``+inf`` where ``mse == 0``."""
+    return -10.0 * torch.log10(torch.as_tensor(mse, dtype=torch.float32))
+
+
 posenc_ddpm = _t.posenc_ddpm
 camera_rays = _t.camera_rays
 posenc_nerf = _t.posenc_nerf
 
 __all__ = ["diffusion_inputs", "diff_loss_nhwc", "group_norm", "gn_film", "conv3x3", "linear", "film_batch", "cat_gn_silu_dense", "cond_conv", "ray_posenc_dir",
            "ray_origin_pe", "ray_conditioning", "attention", "avgpool2", "upsample2",
-           "silu", "logsnr_mlp", "ray_posenc", "posenc_ddpm", "camera_rays", "posenc_nerf", "set_backend",
+           "silu", "logsnr_mlp", "ray_posenc", "image_metrics", "psnr", "posenc_ddpm", "camera_rays", "posenc_nerf", "set_backend",
            "use_hip", "load_library", "library_error", "lib_path"]
 
 

@@ -126,6 +126,8 @@ SIGNATURES = {
     "d3d_wgrad_group_engine": [P],
     "d3d_wgrad_group": [P, I, P, L, P],
     "d3d_wgrad_group_plan": [P, I, IP, IP, C.POINTER(C.c_long)],
+    # metrics.hip (taps: 11 host doubles)
+    "d3d_image_metrics": [P, P, I, I, I, I, I, C.POINTER(C.c_double), P, P, P],
 }
 
 

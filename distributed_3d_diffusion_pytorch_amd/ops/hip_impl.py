@@ -2786,3 +2786,20 @@ def sampler_step(z, eps_c, eps_u, w, alpha, sigma, alpha_n, c, var_sqrt, add_noi
                                w.float().contiguous().data_ptr(), out.data_ptr(), b, D, alpha, sigma, alpha_n, c,
                                var_sqrt, int(add_noise), int(seed), _st()), "sampler_step")
     return out
+
+
+# ------------------------------------------------------------- metrics ---
+_SSIM_TAPS = (ctypes.c_double * 11)(*_t.ssim_window())
+
+
+def image_metrics(pred, target, quantize=True):
+    """(mse [N], ssim [N]) fp32 of two fp32 [N,C,H,W] batches (csrc/metrics.hip:
+    fp64 window sums, fixed-order reductions, two launches)."""
+    x, y = pred.float().contiguous(), target.float().contiguous()
+    N, C, H, W = x.shape
+    blocks = N * C * ((H - 10 + 15) // 16) * ((W - 10 + 15) // 16)     # image_metrics_blocks
+    part = torch.empty(blocks, 2, dtype=torch.float64, device=x.device)
+    out = torch.empty(N, 2, dtype=F32, device=x.device)
+    _chk(_lib.d3d_image_metrics(x.data_ptr(), y.data_ptr(), N, C, H, W, int(bool(quantize)), _SSIM_TAPS,
+                                part.data_ptr(), out.data_ptr(), _st()), "image_metrics")
+    return out[:, 0], out[:, 1]

@@ -353,3 +353,44 @@ def diff_loss_nhwc(y: torch.Tensor, eps: torch.Tensor, loss_type: str = "l2") ->
     if loss_type == "huber":
         return F.smooth_l1_loss(yh, eps.float())
     raise NotImplementedError(loss_type)
+
+
+# ----------------------------------------------------------- image metrics ---
+SSIM_TAPS, SSIM_SIGMA = 11, 1.5
+SSIM_C1, SSIM_C2 = 0.01 ** 2, 0.03 ** 2
+
+
+def ssim_window() -> list:
+    """The normalised 11-tap Gaussian (sigma 1.5) of SSIM, in float64."""
+    g = [math.exp(-((k - SSIM_TAPS // 2) ** 2) / (2.0 * SSIM_SIGMA ** 2)) for k in range(SSIM_TAPS)]
+    s = math.fsum(g)
+    return [v / s for v in g]
+
+
+def image_map01(x: torch.Tensor, quantize: bool) -> torch.Tensor:
+    """[-1, 1] fp32 -> [0, 1] float64; ``quantize``: through the uint8 value
+    ``sampling.py:save_png`` writes (fp32 add, fp32 multiply, truncation)."""
+    c = x.float().clamp(-1.0, 1.0)
+    if quantize:
+        return ((c + 1.0) * 127.5).to(torch.uint8).double() / 255.0
+    return (c.double() + 1.0) * 0.5
+
+
+def image_metrics(pred: torch.Tensor, target: torch.Tensor, quantize: bool = True):
+    """Per-image (mse [N], ssim [N]) fp32 of two [N,C,H,W] batches in [-1, 1]
+    on the [0, 1] scale: the float64 composition (CPU path and oracle of
+    ``image_metrics_tile_k``).  SSIM: Wang et al. 2004, per channel, separable
+    11-tap Gaussian window over the valid region, L = 1."""
+    N, C, H, W = pred.shape
+    x, y = image_map01(pred, quantize), image_map01(target, quantize)
+    mse = (x - y).square().flatten(1).mean(1)
+    g = torch.tensor(ssim_window(), dtype=torch.float64, device=x.device)
+
+    def blur(v):
+        v = v.reshape(N * C, 1, H, W)
+        return F.conv2d(F.conv2d(v, g.view(1, 1, 1, -1)), g.view(1, 1, -1, 1))
+
+    mx, my = blur(x), blur(y)
+    vx, vy, cxy = blur(x * x) - mx * mx, blur(y * y) - my * my, blur(x * y) - mx * my
+    s = ((2 * mx * my + SSIM_C1) * (2 * cxy + SSIM_C2)) / ((mx * mx + my * my + SSIM_C1) * (vx + vy + SSIM_C2))
+    return mse.float(), s.reshape(N, -1).mean(1).float()

@@ -1,0 +1,128 @@
+#!/usr/bin/env python
+"""Evaluation CLI: PSNR / SSIM of generated novel views on held-out objects
+(the 3DiM protocol) and, optionally, the held-out training loss.
+
+    python evaluate.py --model runs/cars64/latest.pt --data data/SRN/cars_train --instances 64
+
+Takes the first ``--instances`` objects of the split (the 90 / 10 rule of the
+training set), conditions on ``--input_view`` of each and generates the views
+listed in ``--views``, one chain per (object, guidance weight); up to
+``--batch`` objects run as one graph-replayed sampler step.  With
+``--autoregressive`` each generated view joins its object's record
+(stochastic conditioning); otherwise every view is generated from the input
+view alone.  The results are scored on the device as the 8-bit PNGs would be,
+and ``<out>/metrics.json`` gets the arguments, one row per (instance, view, w)
+and the per-w means.  ``--save_png`` also writes
+``<out>/<instance>/<view>/{gt,<w>}.png``.  Single process.
+"""
+from __future__ import annotations
+
+import argparse
+import json
+import os
+import sys
+import time
+
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+
+
+def parse(argv=None):
+    ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
+    ap.add_argument("--model", default="./trained_model.pt")
+    ap.add_argument("--data", default="./data/SRN/cars_train", help="SRN instance root")
+    ap.add_argument("--index", default="", help="index pickle/json {instance: [views]}; default: scan --data")
+    ap.add_argument("--split", default="val", choices=["train", "val"])
+    ap.add_argument("--instances", type=int, default=64, help="first N objects of the split (0 = all)")
+    ap.add_argument("--input_view", type=int, default=0)
+    ap.add_argument("--views", default="1,2,3", help="target views (positions in the sorted view list)")
+    ap.add_argument("--w", default="3.0", help="guidance weights, one chain per object each")
+    ap.add_argument("--timesteps", type=int, default=256)
+    ap.add_argument("--imgsize", type=int, default=64)
+    ap.add_argument("--batch", type=int, default=64, help="objects per sampler batch")
+    ap.add_argument("--autoregressive", action="store_true", help="generated views join the record")
+    ap.add_argument("--val_batches", type=int, default=0, help="also score the training loss on this many batches")
+    ap.add_argument("--val_batch_size", type=int, default=16)
+    ap.add_argument("--ema", action="store_true", help="use EMA weights when the checkpoint has them")
+    ap.add_argument("--seed", type=int, default=0)
+    ap.add_argument("--out", default="evaluation")
+    ap.add_argument("--save_png", action="store_true")
+    ap.add_argument("--backend", default="auto")
+    return ap.parse_args(argv)
+
+
+def val_loss(model, cfg, args, dev) -> float:
+    """The training loss on the first ``val_batches * val_batch_size`` pairs of
+    the split, with the fixed validation draw of ``Trainer.validation_loss``."""
+    from distributed_3d_diffusion_pytorch_amd.config import DiffusionConfig
+    from distributed_3d_diffusion_pytorch_amd.data import SRNDataset, collate
+    from distributed_3d_diffusion_pytorch_amd.engine import heldout_loss
+    ds = SRNDataset(args.split, args.data, args.index, args.imgsize, seed=args.seed)
+    n = min(len(ds), args.val_batches * args.val_batch_size)
+    if n == 0:
+        raise ValueError(f"no instances in the {args.split} split of {args.data}")
+    batches = (tuple(t.to(dev) for t in collate([ds[i] for i in range(s, min(s + args.val_batch_size, n))]))
+               for s in range(0, n, args.val_batch_size))
+    dc = cfg.diffusion if cfg is not None else DiffusionConfig()
+    return float(heldout_loss(model, batches, args.seed, dc, model.compute_dtype))
+
+
+def run(args) -> dict:
+    import torch
+    from distributed_3d_diffusion_pytorch_amd import ops
+    from distributed_3d_diffusion_pytorch_amd.engine import evaluate_objects, load_objects, summarize
+    from distributed_3d_diffusion_pytorch_amd.engine.evaluate import load_model
+
+    if args.backend != "auto":
+        ops.set_backend(args.backend)
+    dev = torch.device("cuda", 0) if torch.cuda.is_available() else torch.device("cpu")
+    t0 = time.time()
+    views = [int(v) for v in args.views.split(",")]
+    w = [float(x) for x in args.w.split(",")]
+    model, cfg = load_model(args.model, args.imgsize, dev, args.ema)
+    objects = load_objects(args.data, args.index, args.split, args.instances, args.imgsize,
+                           sorted({args.input_view, *views}))
+    if not objects:
+        raise ValueError(f"no instances in the {args.split} split of {args.data}")
+    os.makedirs(args.out, exist_ok=True)
+
+    def write_pngs(objs, v, out, gt):
+        from sampling import save_png
+        out, gt = out.cpu().numpy(), gt.cpu().numpy()
+        for gi, o in enumerate(objs):
+            d = os.path.join(args.out, o.name, str(v))
+            os.makedirs(d, exist_ok=True)
+            save_png(gt[gi], os.path.join(d, "gt.png"))
+            for i, wv in enumerate(w):
+                save_png(out[gi * len(w) + i], os.path.join(d, f"{wv:g}.png"))
+
+    t1 = time.time()
+    rows, _ = evaluate_objects(model, objects, args.input_view, views, w, args.timesteps, args.batch,
+                               args.autoregressive, args.seed, dev,
+                               on_view=write_pngs if args.save_png else None)
+    if dev.type == "cuda":
+        torch.cuda.synchronize(dev)
+    t2 = time.time()
+    result = {"args": vars(args), "per_image": rows, **summarize(rows)}
+    if args.val_batches > 0:
+        result["val_loss"] = val_loss(model, cfg, args, dev)
+    result["sample_seconds"] = t2 - t1
+    result["wall_seconds"] = time.time() - t0
+    tmp = os.path.join(args.out, "metrics.json.tmp")
+    with open(tmp, "w") as f:
+        json.dump(result, f, indent=1, allow_nan=False)
+    os.replace(tmp, os.path.join(args.out, "metrics.json"))
+    for k in sorted(result["psnr_mean"], key=float):
+        p = result["psnr_mean"][k]
+        print(f"[evaluate] w={k}: PSNR {'n/a' if p is None else format(p, '.3f')} dB  SSIM "
+              f"{result['ssim_mean'][k]:.4f}", flush=True)
+    print(f"[evaluate] {result['n_images']} images ({result['n_identical']} identical) in "
+          f"{result['wall_seconds']:.2f}s -> {os.path.join(args.out, 'metrics.json')}", flush=True)
+    return result
+
+
+def main(argv=None) -> None:
+    run(parse(argv))
+
+
+if __name__ == "__main__":
+    main()

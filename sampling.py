@@ -10,12 +10,16 @@ random already-known view of the chain (stochastic conditioning).  Writes
 ``<out>/{k}/gt.png`` and ``<out>/{k}/{i}.png`` like the reference.
 
 Multi-GPU: ``--gpus N`` (or torchrun) shards the guidance-weight chains over
-ranks, one process per GPU; rank 0 gathers and writes the PNGs.
+ranks, one process per GPU; rank 0 gathers and writes the PNGs.  ``--metrics``
+also scores every generated image against its ground truth (as written: 8-bit)
+and writes ``<out>/metrics.json``.
 """
 from __future__ import annotations
 
 import argparse
 import glob
+import json
+import math
 import os
 import sys
 import time
@@ -39,6 +43,8 @@ def parse(argv=None):
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--gpus", type=int, default=0)
     ap.add_argument("--backend", default="auto")
+    ap.add_argument("--metrics", action="store_true",
+                    help="also write <out>/metrics.json: PSNR / SSIM of every (view, chain) against gt.png")
     return ap.parse_args(argv)
 
 
@@ -68,28 +74,16 @@ def run(args) -> None:
     import torch
     import torch.distributed as dist
     from distributed_3d_diffusion_pytorch_amd import ops
-    from distributed_3d_diffusion_pytorch_amd.models import XUNet
     from distributed_3d_diffusion_pytorch_amd.engine import DiffusionSampler, RecordEntry, shard_range
+    from distributed_3d_diffusion_pytorch_amd.engine.evaluate import load_model
     from distributed_3d_diffusion_pytorch_amd.parallel import init_distributed, cleanup
-    from distributed_3d_diffusion_pytorch_amd.utils import load_checkpoint, load_model_weights
 
     ctx = init_distributed("auto")
     dev = ctx.device
     if args.backend != "auto":
         ops.set_backend(args.backend)
     imgs, Rs, Ts, K = load_instance(args.target, args.imgsize)
-    ck = load_checkpoint(args.model)
-    if isinstance(ck.get("config"), dict):       # our checkpoints carry their model config
-        from distributed_3d_diffusion_pytorch_amd.config import from_dict
-        mcfg = from_dict(ck["config"]).model
-        mcfg.H = mcfg.W = args.imgsize
-        model = XUNet(mcfg).to(dev)
-    else:                                        # reference checkpoints: XUNet(H, W, ch=128)
-        model = XUNet(H=args.imgsize, W=args.imgsize, ch=128).to(dev)
-    sd = ck.get("ema") if (args.ema and ck.get("ema")) else ck["model"]
-    load_model_weights(model, sd)
-    model.compute_dtype = torch.bfloat16 if dev.type == "cuda" else torch.float32
-    model.eval()
+    model, _ = load_model(args.model, args.imgsize, dev, args.ema)
 
     w_all = torch.tensor([float(x) for x in args.w.split(",")])
     s, e = shard_range(len(w_all), ctx.rank, ctx.world)
@@ -106,6 +100,7 @@ def run(args) -> None:
         save_png(imgs[0], os.path.join(args.out, "0", "gt.png"))
     nviews = len(imgs) if not args.max_views else min(len(imgs), args.max_views + 1)
     Kt = t(K)
+    rows = []
     for k in range(1, nviews):
         t0 = time.time()
         out = sampler.sample(record, t(Rs[k]), t(Ts[k]), Kt, w) if b > 0 else \
@@ -128,7 +123,15 @@ def run(args) -> None:
             arr = full.float().cpu().numpy()
             for i in range(arr.shape[0]):
                 save_png(arr[i], os.path.join(d, f"{i}.png"))
+            if args.metrics:
+                mse, ssim = ops.image_metrics(full.float(), t(imgs[k])[None].expand_as(full), quantize=True)
+                for i, (m, sv) in enumerate(zip(mse.double().cpu().tolist(), ssim.double().cpu().tolist())):
+                    rows.append({"view": k, "chain": i, "w": float(w_all[i]), "mse": m,
+                                 "psnr": 10.0 * math.log10(1.0 / m) if m > 0 else None, "ssim": sv})
             print(f"[sampling] view {k}/{nviews - 1}: {time.time() - t0:.2f}s", flush=True)
+    if args.metrics and ctx.is_main:
+        with open(os.path.join(args.out, "metrics.json"), "w") as f:
+            json.dump({"target": args.target, "per_image": rows}, f, indent=1, allow_nan=False)
     cleanup()
 
 

@@ -27,7 +27,8 @@ def parse(argv=None):
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--transfer", default="", help="resume from <dir>/latest.pt (reference flag)")
     ap.add_argument("--train_data", default="", help="SRN instance root (Lightning-CLI flag)")
-    ap.add_argument("--val_data", default="", help="accepted for CLI compatibility (unused, as upstream)")
+    ap.add_argument("--val_data", default="", help="SRN instance root for the validation loss (its held-out "
+                                                   "split; logged every val_every=N steps, default never)")
     ap.add_argument("--index", default="", help="index pickle/json {instance: [views]}; default <data>/cars.pickle")
     ap.add_argument("--preset", default="", help="config preset (chairs32_cpu, cars64_8gpu, ...)")
     ap.add_argument("--synthetic", action="store_true", help="on-device synthetic SRN-shaped data")
@@ -56,6 +57,8 @@ def run(args) -> None:
                     break
     if args.index:
         cfg.data.index = args.index
+    if args.val_data:
+        cfg.data.val_path = args.val_data
     if args.synthetic:
         cfg.data.synthetic = True
     if args.transfer:
