@@ -45,7 +45,6 @@ SIGNATURES = {
     "d3d_attn_fwd_cfg": [I],
     "d3d_colsum_jobs": [P, I, P],
     "d3d_conv_halo_cfg": [I],
-    "d3d_conv_res_cfg": [I],
     # elementwise.hip
     "d3d_period_sum": [P, P, I, L, P],
     "d3d_silu": [P, P, L, P],
@@ -66,30 +65,21 @@ SIGNATURES = {
     "d3d_adam": [P, P, P, P, P, L, F, F, F, F, F, F, F, F, P],
     "d3d_adam_dev": [P, P, P, P, P, L, P, P],
     # conv.hip
-    "d3d_conv3x3": [P, P, P, P, P, P, I, I, I, I, I, I, I, I, I, I, I, F, I, P],
-    "d3d_conv_wgrad_plan": [I, I, I, I, I, IP, IP],
-    "d3d_conv3x3_wgrad": [P, P, P, P, I, I, I, I, I, I, I, I, I, I, I, P],
     "d3d_chansum": [P, P, P, P, I, I, I, I, P],
     "d3d_colsum": [P, L, I, P, P, P, I, P],
-    "d3d_pack_conv_weight": [P, P, I, I, I, I, I, P],
-    "d3d_conv": [P, P, P, P, P, P, I, I, I, I, I, I, I, I, I, I, I, F, I, I, P, I, P],
-    "d3d_conv2": [P, P, P, P, P, P, I, I, I, I, I, I, I, I, I, I, I, F, I, I, P, I, P, I, IP, P],
     "d3d_conv3_gn_ok": [I, I, I, I, I],
     "d3d_conv3_gn": [P, P, P, P, I, I, I, I, I, I, P, I, IP, P, P],
     "d3d_conv3": [P, P, P, P, P, P, I, I, I, I, I, I, I, I, I, I, I, F, I, I, P, I, P, I, IP, P, IP, P],
     "d3d_conv_plan": [I, I, I, I, I, I],
-    "d3d_set_conv_korder": [I],
     "d3d_set_wgrad_impl": [I],
     "d3d_conv_wgrad_plan2": [I, I, I, I, I, I, IP, IP],
     "d3d_conv_wgrad_plan3": [I, I, I, I, I, I, I, I, I, IP, IP],
-    "d3d_conv_wgrad": [P, P, P, P, I, I, I, I, I, I, I, I, I, I, I, I, P],
     "d3d_pack_weight": [P, P, I, I, I, I, I, I, P],
     "d3d_set_conv_impl": [I, P],
     "d3d_pack_all": [P, P, I, P],
     "d3d_conv_wgrad_cat": [P, P, P, I, P, P, P, I, I, I, I, I, I, P],
     "d3d_conv_wgrad_seg": [P, P, P, I, I, I, I, I, I, I, I, I, I, I, I, I, P, P, P, P],
     "d3d_wgrad_scatter": [P, I, I, I, I, P, I, I, P, P, P, P],
-    "d3d_conv_wgrad2": [P, P, P, P, P, I, I, I, I, I, I, I, I, I, I, I, I, P],
     "d3d_conv_wgrad3": [P, P, P, P, P, I, I, I, I, I, I, I, I, I, I, I, I, F, P],
     # rays.hip
     "d3d_ray_posenc": [P, P, P, P, P, P, P, P, I, I, I, P],

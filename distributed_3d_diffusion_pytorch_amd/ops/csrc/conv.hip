@@ -3,7 +3,8 @@
 // Replaces the 76 Conv2d(3x3) of the X-UNet (xunet.py:114-126,294-297,385,
 // 473): 54 % of the model FLOPs (+12 % for the strided conditioning convs).
 //
-// Forward / dgrad kernel (conv_igemm_k):
+// Forward / dgrad kernels (the implicit-GEMM family conv_glds_k, conv_bufl_k,
+// conv_w8_k; conv_halo_k and conv_small.hip stage the input differently):
 //   D[co][pix] = sum_k Wp[co][k] * im2col(I)[k][pix],   k = (tap, ci)
 //   * A operand = packed weights [OC_pad][9][IC_pad] bf16 (K-contiguous rows),
 //     B operand = im2col gathered on the fly from NHWC input (each pixel's
@@ -13,21 +14,22 @@
 //     8 contiguous bytes per lane;
 //   * 128x128 block tile, BK=64 (one tap x 64 channels), 4 waves (2x2), each
 //     wave 64x64 = 4x4 v_mfma_f32_16x16x32_bf16 tiles, fp32 accumulate;
-//   * register-staged double-buffered LDS (global loads for step t+1 in
-//     flight while step t's MFMAs run), XOR-swizzled 128-byte LDS rows so the
+//   * double-buffered LDS filled by LDS-DMA (the loads for step t+1 in flight
+//     while step t's MFMAs run), XOR-swizzled 128-byte LDS rows so the
 //     ds_read_b128 fragment reads are conflict-free;
 //   * zero-fill for padding / out-of-range taps / channel tails in the loader;
 //   * fused epilogue: + bias[co] + row_bias[image][co] (+ residual) * scale;
 //   * TRANS=true computes the input gradient of a strided conv
 //     (src = (o + 1 - k) / s when divisible) with weights packed [ci][tap][co].
 //
-// Weight gradient kernel (conv_wgrad_k):
+// Weight gradient kernels (conv_wgrad_k, conv_wgrad_bufl_k, conv_wgrad_w8_k):
 //   dW[co][(tap,ci)] = sum_pix dY[pix][co] * I[src(pix,tap)][ci]
 //   both operands have the reduction (pixel) axis as their SLOW memory axis,
 //   so tiles are stored pixel-major in LDS and MFMA fragments are read with
-//   the gfx950 transpose read ds_read_b64_tr_b16; rows are padded by 32 B and
-//   the pixel order inside a 32-pixel step is permuted identically for both
-//   operands so that every transpose read is bank-conflict free.  Split-K over
+//   the gfx950 transpose read ds_read_b64_tr_b16; in conv_wgrad_k rows are
+//   padded by 32 B and the pixel order inside a 32-pixel step is permuted
+//   identically for both operands so that every transpose read is
+//   bank-conflict free (the LDS-DMA kernels swizzle instead).  Split-K over
 //   pixels with fp32 partial slabs + a deterministic reduce kernel that also
 //   writes the OIHW layout of the parameter gradient.
 #include "common.h"
@@ -44,179 +46,10 @@ typedef __attribute__((address_space(3))) s16x4 lds_s16x4;
 
 namespace {
 
-constexpr int BK = 64;
-
-template <int BM, int BN, bool TRANS, int TAPS>
-__global__ void __launch_bounds__(256, 2)
-conv_igemm_k(const bf16* __restrict__ I, const bf16* __restrict__ Wp, const float* __restrict__ bias,
-             const float* __restrict__ row_bias, const bf16* __restrict__ res, bf16* __restrict__ O, int Nimg,
-             int IH, int IW, int IC, int ICp, int OH, int OW, int OC, int ldo, int stride, float scale,
-             int res_nmod) {
-  constexpr int WM = BM / 2, WN = BN / 2;       // 2x2 waves
-  constexpr int TM = WM / 16, TN = WN / 16;     // MFMA tiles per wave
-  constexpr int A_LD = BM * BK / 8 / 256;       // 16B loads per thread
-  constexpr int B_LD = BN * BK / 8 / 256;
-  __shared__ __attribute__((aligned(16))) bf16 smem[2 * (BM + BN) * BK];
-  bf16* As = smem;
-  bf16* Bs = smem + 2 * BM * BK;
-
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int wm = wave >> 1, wn = wave & 1;
-  const long Mpix = (long)Nimg * OH * OW;
-  // XCD-aware remap: neighbouring pixel tiles (which share input rows and
-  // the whole weight panel) land on the same XCD's L2.
-  const int nbx = gridDim.x;
-  int bid = blockIdx.x;
-  {
-    int q = nbx / 8, r = nbx % 8, xcd = bid % 8;
-    bid = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + bid / 8;
-  }
-  const long n0 = (long)bid * BN;               // pixel tile start
-  const int m0 = blockIdx.y * BM;               // output-channel tile start
-  const int Kp = TAPS * ICp;
-
-  // per-thread B rows (pixels): fixed over the K loop
-  const int cb = tid & 7;                        // 16B chunk within the BK row
-  int pn[B_LD], poh[B_LD], pow_[B_LD];
-  bool pvalid[B_LD];
-#pragma unroll
-  for (int i = 0; i < B_LD; ++i) {
-    long p = n0 + (tid >> 3) + i * 32;
-    pvalid[i] = p < Mpix;
-    long pp = pvalid[i] ? p : 0;
-    pow_[i] = (int)(pp % OW);
-    long t = pp / OW;
-    poh[i] = (int)(t % OH);
-    pn[i] = (int)(t / OH);
-  }
-
-  bf16x8 ra[A_LD], rb[B_LD];
-  const bf16x8 zero8 = {};
-  auto gload = [&](int kstep) {
-    const int tap = TAPS == 9 ? kstep / (ICp / BK) : 0;
-    const int c0 = (TAPS == 9 ? kstep % (ICp / BK) : kstep) * BK;
-    const int kh = TAPS == 9 ? tap / 3 : 1, kw = TAPS == 9 ? tap % 3 : 1;   // 1x1 == centre tap
-#pragma unroll
-    for (int i = 0; i < A_LD; ++i) {
-      int r = (tid >> 3) + i * 32;
-      ra[i] = *reinterpret_cast<const bf16x8*>(Wp + (long)(m0 + r) * Kp + tap * ICp + c0 + cb * 8);
-    }
-    const int c = c0 + cb * 8;
-#pragma unroll
-    for (int i = 0; i < B_LD; ++i) {
-      int ih, iw;
-      bool ok = pvalid[i] && c < IC;
-      if (!TRANS) {
-        ih = poh[i] * stride + kh - 1;
-        iw = pow_[i] * stride + kw - 1;
-      } else if (stride == 1) {      // wave-uniform: no integer division in the common case
-        ih = poh[i] + 1 - kh;
-        iw = pow_[i] + 1 - kw;
-      } else {
-        int th = poh[i] + 1 - kh, tw = pow_[i] + 1 - kw;
-        ok = ok && th >= 0 && tw >= 0 && (th % stride) == 0 && (tw % stride) == 0;
-        ih = th / stride;
-        iw = tw / stride;
-      }
-      ok = ok && ih >= 0 && ih < IH && iw >= 0 && iw < IW;
-      rb[i] = ok ? *reinterpret_cast<const bf16x8*>(I + (((long)pn[i] * IH + ih) * IW + iw) * IC + c) : zero8;
-    }
-  };
-  auto swz = [](int row, int chunk) { return row * BK + ((chunk ^ (row & 7)) << 3); };
-  auto swrite = [&](int buf) {
-    bf16* a = As + buf * BM * BK;
-    bf16* b = Bs + buf * BN * BK;
-#pragma unroll
-    for (int i = 0; i < A_LD; ++i) *reinterpret_cast<bf16x8*>(a + swz((tid >> 3) + i * 32, cb)) = ra[i];
-#pragma unroll
-    for (int i = 0; i < B_LD; ++i) *reinterpret_cast<bf16x8*>(b + swz((tid >> 3) + i * 32, cb)) = rb[i];
-  };
-
-  f32x4 acc[TM][TN];
-#pragma unroll
-  for (int i = 0; i < TM; ++i)
-#pragma unroll
-    for (int j = 0; j < TN; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
-
-  const int nk = Kp / BK;
-  gload(0);
-  swrite(0);
-  __syncthreads();
-  const int fr = lane & 15, fq = lane >> 4;
-  for (int ks = 0; ks < nk; ++ks) {
-    const int buf = ks & 1;
-    if (ks + 1 < nk) gload(ks + 1);
-    const bf16* a = As + buf * BM * BK;
-    const bf16* b = Bs + buf * BN * BK;
-#pragma unroll
-    for (int kk = 0; kk < BK / 32; ++kk) {
-      bf16x8 af[TM], bfr[TN];
-#pragma unroll
-      for (int i = 0; i < TM; ++i) {
-        int row = wm * WM + i * 16 + fr;
-        af[i] = *reinterpret_cast<const bf16x8*>(a + swz(row, kk * 4 + fq));
-      }
-#pragma unroll
-      for (int j = 0; j < TN; ++j) {
-        int row = wn * WN + j * 16 + fr;
-        bfr[j] = *reinterpret_cast<const bf16x8*>(b + swz(row, kk * 4 + fq));
-      }
-#pragma unroll
-      for (int i = 0; i < TM; ++i)
-#pragma unroll
-        for (int j = 0; j < TN; ++j)
-          acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(af[i], bfr[j], acc[i][j], 0, 0, 0);
-    }
-    if (ks + 1 < nk) swrite(buf ^ 1);
-    __syncthreads();
-  }
-
-  // ---- epilogue: D[co][pix] -> O[pix][co] (NHWC) ----
-  const int OHW = OH * OW;
-#pragma unroll
-  for (int j = 0; j < TN; ++j) {
-    long pix = n0 + wn * WN + j * 16 + fr;
-    if (pix >= Mpix) continue;
-    int img = (int)(pix / OHW);
-#pragma unroll
-    for (int i = 0; i < TM; ++i) {
-      int co = m0 + wm * WM + i * 16 + fq * 4;
-      if (co >= OC) continue;
-      float v[4];
-#pragma unroll
-      for (int e = 0; e < 4; ++e) {
-        int c = co + e < OC ? co + e : OC - 1;
-        float t = acc[i][j][e] + (bias ? bias[c] : 0.f);
-        if (row_bias) t += row_bias[(long)img * OC + c];
-        v[e] = t;
-      }
-      bf16* dst = O + pix * ldo + co;
-      // residual row: same pixel, or (image % res_nmod) for a residual that is
-      // broadcast over the batch (per-frame conditioning term)
-      const long rpix = res_nmod > 0 ? (long)(img % res_nmod) * OHW + (pix - (long)img * OHW) : pix;
-      if (co + 3 < OC && (ldo & 3) == 0) {
-        if (res) {
-          bf16x4 r4 = *reinterpret_cast<const bf16x4*>(res + rpix * ldo + co);
-#pragma unroll
-          for (int e = 0; e < 4; ++e) v[e] += (float)r4[e];
-        }
-        bf16x4 o4;
-#pragma unroll
-        for (int e = 0; e < 4; ++e) o4[e] = (bf16)(v[e] * scale);
-        *reinterpret_cast<bf16x4*>(dst) = o4;
-      } else {
-        for (int e = 0; e < 4 && co + e < OC; ++e) {
-          float t = v[e];
-          if (res) t += (float)res[rpix * ldo + co + e];
-          dst[e] = (bf16)(t * scale);
-        }
-      }
-    }
-  }
-}
-
 // ---------------------------------------------------- glds pipeline ------
-// Same GEMM as conv_igemm_k, but operand tiles go global -> LDS directly
+// The catch-all of the forward / dgrad ladder (transposed convs with stride
+// > 1, operands past the 32-bit buffer offsets): flat 64-bit addresses, so
+// no operand size limit.  Operand tiles go global -> LDS directly
 // (global_load_lds_dwordx4: no VGPR staging, no ds_write), double-buffered
 // with a COUNTED vmcnt so the next tile's DMA stays in flight across the raw
 // s_barrier while the current tile's MFMAs run.  LDS images are lane-linear
@@ -415,7 +248,7 @@ conv_glds_k(const bf16* __restrict__ I, const bf16* __restrict__ Wp, const float
 
 // fused GroupNorm statistics: gn_part_store (common.h)
 
-template <int TAPS, bool TRANS, bool ONEBAR>
+template <int TAPS, bool TRANS>
 __global__ void __launch_bounds__(256, 2)
 conv_bufl_k(const bf16* __restrict__ I, const bf16* __restrict__ Wp, const float* __restrict__ bias,
             const float* __restrict__ row_bias, const bf16* __restrict__ res, bf16* __restrict__ O,
@@ -522,7 +355,9 @@ conv_bufl_k(const bf16* __restrict__ I, const bf16* __restrict__ Wp, const float
   const int nk = k1 - k0;
   const int fr = lane & 15, fq = lane >> 4;
   const int OHW = OH * OW;
-  // residual prefetch (see conv_halo_k); not on split-K partial launches
+  // residual prefetch into registers ahead of the K loop (its reads are
+  // exposed in the epilogue otherwise, see conv_halo_k); not on split-K
+  // partial launches
   bf16x4 rres[TM][TN];
   const bool pre_res = res != nullptr && part == nullptr && (ldo & 3) == 0;
   if (pre_res) {
@@ -541,35 +376,23 @@ conv_bufl_k(const bf16* __restrict__ I, const bf16* __restrict__ Wp, const float
     }
   }
   issue(k0, 0);
-  if (ONEBAR) {
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    if (pre_res) {
+  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+  if (pre_res) {
 #pragma unroll
-      for (int i = 0; i < TM; ++i)
+    for (int i = 0; i < TM; ++i)
 #pragma unroll
-        for (int j = 0; j < TN; ++j) asm volatile("" ::"v"(__builtin_bit_cast(unsigned long long, rres[i][j])));
-    }
-    __builtin_amdgcn_s_barrier();
+      for (int j = 0; j < TN; ++j) asm volatile("" ::"v"(__builtin_bit_cast(unsigned long long, rres[i][j])));
   }
+  __builtin_amdgcn_s_barrier();
   for (int ks = 0; ks < nk; ++ks) {
     const int st = ks & 1;
-    if (ONEBAR) {
-      // one barrier per k-step (cdna guide T3/T4 "minimum 2-phase"): stage
-      // the next tile first (its buffer was last read before the previous
-      // barrier), compute this one at raised priority, then wait + barrier
-      if (ks + 1 < nk) issue(k0 + ks + 1, st ^ 1);
-    } else {
-      if (ks + 1 < nk) {
-        issue(k0 + ks + 1, st ^ 1);
-        asm volatile("s_waitcnt vmcnt(8)" ::: "memory");     // retire stage st, keep st^1 in flight
-      } else {
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-      }
-      __builtin_amdgcn_s_barrier();
-    }
+    // one barrier per k-step (cdna guide T3/T4 "minimum 2-phase"): stage
+    // the next tile first (its buffer was last read before the previous
+    // barrier), compute this one at raised priority, then wait + barrier
+    if (ks + 1 < nk) issue(k0 + ks + 1, st ^ 1);
     const bf16* a = smem + st * STAGE;
     const bf16* b = a + BM * BKk;
-    if (ONEBAR) __builtin_amdgcn_s_setprio(1);
+    __builtin_amdgcn_s_setprio(1);
 #pragma unroll
     for (int kk = 0; kk < BKk / 32; ++kk) {
       bf16x8 af[TM], bfr[TN];
@@ -583,14 +406,9 @@ conv_bufl_k(const bf16* __restrict__ I, const bf16* __restrict__ Wp, const float
         for (int j = 0; j < TN; ++j)
           acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(af[i], bfr[j], acc[i][j], 0, 0, 0);
     }
-    if (ONEBAR) {
-      __builtin_amdgcn_s_setprio(0);
-      asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
-      __builtin_amdgcn_s_barrier();                           // next stage landed everywhere; this one free
-      continue;
-    }
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    __builtin_amdgcn_s_barrier();                             // stage st free for reuse
+    __builtin_amdgcn_s_setprio(0);
+    asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
+    __builtin_amdgcn_s_barrier();                             // next stage landed everywhere; this one free
   }
 
   if (part) {
@@ -803,8 +621,9 @@ conv_w8_k(const bf16* __restrict__ I, const bf16* __restrict__ Wp, const float* 
   const int nk = Kp / BKk;
   const int fr = lane & 15, fq = lane >> 4;
   const int OHW = OH * OW;
-  // residual prefetch (see conv_halo_k): issued ahead of the first stage,
-  // drained with it, held in registers through the K loop
+  // residual prefetch (its reads are exposed in the epilogue otherwise, see
+  // conv_halo_k): issued ahead of the first stage, drained with it, held in
+  // registers through the K loop
   bf16x4 rres[RES ? TM : 1][RES ? TN : 1];
   const bool vec_out = (ldo & 3) == 0;
   if (RES && res && vec_out) {
@@ -985,15 +804,15 @@ __device__ __forceinline__ void halo_issue_b(bf16* sH, const bf16* I, int in_byt
                                              hoff[k] + (unsigned)cbyte, 0, 0, 0);
 }
 
-// AU: the nine taps unrolled with every B-fragment LDS offset precomputed
-// (9 x TN registers): the swizzled address of a tap-shifted halo pixel is not
-// linear in the shift, and computing it per step cost ~48 VALU per 32 MFMAs
-// on the critical path between the barrier and the first MFMA.  (Without the
-// residual prefetch only: with it the register file overflows.)
-// P2 (with AU): one barrier per PAIR of taps over an 8-slot weight ring (the
+// The nine taps are unrolled with every B-fragment LDS offset precomputed
+// (3 x TN registers per kw; the kh shift is a constant): the swizzled address
+// of a tap-shifted halo pixel is not linear in the shift, and computing it per
+// step cost ~48 VALU per 32 MFMAs on the critical path between the barrier and
+// the first MFMA.
+// P2: one barrier per PAIR of taps over an 8-slot weight ring (the
 // LDS budget of the 64-wide tile: 2 x 48 KB halo + 64 KB ring = all 160 KB);
 // halves the per-MFMA barrier / wait cost.  Needs an even chunk count.
-// GNA (with AU, forward, single taps per barrier): the input is the
+// GNA (forward, single taps per barrier): the input is the
 // PRE-GroupNorm tensor x and the conv runs on silu(x * A + B) -- the
 // ResnetBlock's GN0 + SiLU folded into the halo staging (gab [Nimg][IC][2] =
 // (A, B) per image and channel, norm.hip gn_ab_k; the image's rows of it sit
@@ -1003,14 +822,13 @@ __device__ __forceinline__ void halo_issue_b(bf16* sH, const bf16* I, int in_byt
 // publishes it; pads stay zero.  (Not on the tap-pair schedule: its 160 KB of
 // LDS leave no room for the table, and the 16 (A, B) registers it would hold
 // instead spill it.)
-template <int OWT, bool TRANS, int BNT = 512, bool PF = false, bool RES = true, bool AU = false, bool P2 = false,
-          bool GNA = false>
+template <int OWT, bool TRANS, int BNT = 512, bool RES = true, bool P2 = false, bool GNA = false>
 __global__ void __launch_bounds__(512, 1)
 conv_halo_k(const bf16* __restrict__ I, const bf16* __restrict__ Wp, const float* __restrict__ bias,
             const float* __restrict__ row_bias, const bf16* __restrict__ res, bf16* __restrict__ O, int in_bytes,
             int w_bytes, int Nimg, int OH, int IC, int ICp, int OC, float scale, int res_nmod,
             float* __restrict__ gnp, int gn_groups, bf16* __restrict__ O2, const float* __restrict__ gab) {
-  static_assert(!GNA || (AU && !P2 && !TRANS && !PF), "GroupNorm staging: forward, unrolled single-tap schedule");
+  static_assert(!GNA || (!P2 && !TRANS), "GroupNorm staging: forward, single-tap schedule");
   __shared__ __attribute__((aligned(16))) float sG[GNA ? 2 * 512 : 4];
   typedef HaloGeom<OWT, BNT> Gm;
   constexpr int BM = 128, BN = BNT, WM = 64, WN = BN / 4, TM = 4, TN = WN / 16;
@@ -1105,16 +923,13 @@ conv_halo_k(const bf16* __restrict__ I, const bf16* __restrict__ Wp, const float
     hp0[j] = (p / OWT) * Gm::HW2 + (p % OWT);
   }
   const int OHW = OH * OW;
-  // Residual prefetch: issued ahead of the first operand DMA and drained by
-  // its full wait, then held in registers through the K loop.  In the
-  // epilogue the 8-byte residual reads (16 pixels x 32 B per instruction)
-  // were fully exposed -- one block per CU, nothing left to overlap them --
-  // and cost +30 % on the level-0 conv (tools/kbench_conv_epi.py).
-  // AU: the residual goes straight into the accumulators instead (the
-  // epilogue computes (acc + bias + res) * scale either way), which frees
-  // the 64 prefetch registers the unrolled-tap offsets need
-  constexpr bool RPF = RES && !AU;
-  bf16x4 rres[RPF ? TM : 1][RPF ? TN : 1];
+  // Residual preload: read ahead of the first operand DMA, straight into the
+  // accumulators (the epilogue computes (acc + bias + res) * scale either
+  // way).  In the epilogue the 8-byte residual reads (16 pixels x 32 B per
+  // instruction) were fully exposed -- one block per CU, nothing left to
+  // overlap them -- and cost +30 % on the level-0 conv
+  // (tools/kbench_conv_epi.py); held in registers of their own through the K
+  // loop they took the 64 registers the unrolled-tap offsets need.
   if (RES && res) {
 #pragma unroll
     for (int j = 0; j < TN; ++j) {
@@ -1124,77 +939,13 @@ conv_halo_k(const bf16* __restrict__ I, const bf16* __restrict__ Wp, const float
       for (int i = 0; i < TM; ++i) {
         const int co = m0 + wm * WM + i * 16 + fq * 4;
         const bf16x4 r4 = co < OC ? *reinterpret_cast<const bf16x4*>(res + rpix * OC + co) : bf16x4{};
-        if constexpr (RPF) {
-          rres[i][j] = r4;
-        } else {
 #pragma unroll
-          for (int e = 0; e < 4; ++e) acc[i][j][e] = (float)r4[e];
-        }
+        for (int e = 0; e < 4; ++e) acc[i][j][e] = (float)r4[e];
       }
     }
   }
 
-  auto frags = [&](bf16x8 (&af)[TM], bf16x8 (&bfr)[TN], const bf16* a, const bf16* hb, int t) {
-    const int kh = TRANS ? 2 - t / 3 : t / 3, kw = TRANS ? 2 - t % 3 : t % 3;
-    const int dsh = kh * Gm::HW2 + kw;
-#pragma unroll
-    for (int j = 0; j < TN; ++j) {
-      const int hp = hp0[j] + dsh;
-      bfr[j] = *reinterpret_cast<const bf16x8*>(hb + hp * HALO_CH + ((fq ^ ((hp >> 1) & 2)) << 3));
-    }
-#pragma unroll
-    for (int i = 0; i < TM; ++i) {
-      const int row = wm * WM + i * 16 + fr;
-      af[i] = *reinterpret_cast<const bf16x8*>(a + row * HALO_CH + ((fq ^ ((row >> 1) & 2)) << 3));
-    }
-  };
-  if constexpr (PF) {
-    // fragment double-buffering: step s+1's weights are waited for at step
-    // s's barrier (ring issue distance 4), so its LDS fragment reads go out
-    // while step s's MFMAs run instead of in front of them
-    halo_issue_b<Gm::HPW>(sH, I, in_bytes, hoff, 0, wave);
-#pragma unroll
-    for (int k = 0; k < 4; ++k) halo_issue_a(sAr + k * Gm::ABUF, Wp, w_bytes, aoff, a_soff(k), wave);
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __builtin_amdgcn_s_barrier();
-    bf16x8 af[TM], bfr[TN];
-    frags(af, bfr, sAr, sH, 0);
-    int s = 0;
-    for (int c = 0; c < NCH; ++c) {
-#pragma unroll 1
-      for (int t = 0; t < 9; ++t, ++s) {
-        // (lgkmcnt(0): the prefetched fragments of this slot must be read
-        // before the barrier frees it for the DMA below)
-        if (t >= 1 && t <= 3) {
-          asm volatile("s_waitcnt vmcnt(%0) lgkmcnt(0)" ::"n"(2 + Gm::HPW) : "memory");
-        } else {
-          asm volatile("s_waitcnt vmcnt(2) lgkmcnt(0)" ::: "memory");
-        }
-        __builtin_amdgcn_s_barrier();
-        halo_issue_a(sAr + ((s + 4) & 3) * Gm::ABUF, Wp, w_bytes, aoff, a_soff(s + 4), wave);
-        if (t == 0) {
-          const int cn = c + 1 < NCH ? c + 1 : NCH - 1;
-          halo_issue_b<Gm::HPW>(sH + ((c + 1) & 1) * Gm::HBUF, I, in_bytes, hoff, cn * HALO_CH * 2, wave);
-        }
-        bf16x8 an[TM], bn[TN];
-        if (s + 1 < S) {
-          const int cn = t == 8 ? c + 1 : c, tn = t == 8 ? 0 : t + 1;
-          frags(an, bn, sAr + ((s + 1) & 3) * Gm::ABUF, sH + (cn & 1) * Gm::HBUF, tn);
-        }
-        __builtin_amdgcn_s_setprio(1);
-#pragma unroll
-        for (int i = 0; i < TM; ++i)
-#pragma unroll
-          for (int j = 0; j < TN; ++j)
-            acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(af[i], bfr[j], acc[i][j], 0, 0, 0);
-        __builtin_amdgcn_s_setprio(0);
-#pragma unroll
-        for (int i = 0; i < TM; ++i) af[i] = an[i];
-#pragma unroll
-        for (int j = 0; j < TN; ++j) bfr[j] = bn[j];
-      }
-    }
-  } else if constexpr (AU && P2) {
+  if constexpr (P2) {
   // prologue: halo of chunk 0, weights of steps 0..3
   halo_issue_b<Gm::HPW>(sH, I, in_bytes, hoff, 0, wave);
 #pragma unroll
@@ -1255,7 +1006,7 @@ conv_halo_k(const bf16* __restrict__ I, const bf16* __restrict__ Wp, const float
       __builtin_amdgcn_s_setprio(0);
     }
   }
-  } else if constexpr (AU) {
+  } else {
   float gt[GNA ? 2 : 1];
   if constexpr (GNA) {                         // this image's (A, B) rows: into LDS behind the prologue DMAs
 #pragma unroll
@@ -1325,62 +1076,6 @@ conv_halo_k(const bf16* __restrict__ I, const bf16* __restrict__ Wp, const float
       __builtin_amdgcn_s_setprio(0);
     }
   }
-  } else {
-  halo_issue_b<Gm::HPW>(sH, I, in_bytes, hoff, 0, wave);
-  halo_issue_a(sAr, Wp, w_bytes, aoff, a_soff(0), wave);
-  halo_issue_a(sAr + Gm::ABUF, Wp, w_bytes, aoff, a_soff(1), wave);
-  halo_issue_a(sAr + 2 * Gm::ABUF, Wp, w_bytes, aoff, a_soff(2), wave);
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-  if constexpr (RES) {
-    if (res) {
-      // pin the prefetched values here (keeps the loads ahead of the K loop)
-#pragma unroll
-      for (int i = 0; i < TM; ++i)
-#pragma unroll
-        for (int j = 0; j < TN; ++j) asm volatile("" ::"v"(__builtin_bit_cast(unsigned long long, rres[i][j])));
-    }
-  }
-
-  for (int c = 0; c < NCH; ++c) {
-    const bf16* hb = sH + (c & 1) * Gm::HBUF;
-#pragma unroll 1
-    for (int t = 0; t < 9; ++t) {
-      const int s = c * 9 + t;
-      // this step's weights landed; newer loads may stay in flight
-      if (t >= 1 && t <= 3) {                     // (wave-uniform branch)
-        asm volatile("s_waitcnt vmcnt(%0)" ::"n"(2 + Gm::HPW) : "memory");
-      } else {
-        asm volatile("s_waitcnt vmcnt(2)" ::: "memory");
-      }
-      __builtin_amdgcn_s_barrier();
-      halo_issue_a(sAr + ((s + 3) & 3) * Gm::ABUF, Wp, w_bytes, aoff, a_soff(s + 3), wave);
-      if (t == 0) {
-        const int cn = c + 1 < NCH ? c + 1 : NCH - 1;
-        halo_issue_b<Gm::HPW>(sH + ((c + 1) & 1) * Gm::HBUF, I, in_bytes, hoff, cn * HALO_CH * 2, wave);
-      }
-      const bf16* a = sAr + (s & 3) * Gm::ABUF;
-      const int kh = TRANS ? 2 - t / 3 : t / 3, kw = TRANS ? 2 - t % 3 : t % 3;
-      const int dsh = kh * Gm::HW2 + kw;
-      __builtin_amdgcn_s_setprio(1);
-      bf16x8 af[TM], bfr[TN];
-#pragma unroll
-      for (int j = 0; j < TN; ++j) {
-        const int hp = hp0[j] + dsh;
-        bfr[j] = *reinterpret_cast<const bf16x8*>(hb + hp * HALO_CH + ((fq ^ ((hp >> 1) & 2)) << 3));
-      }
-#pragma unroll
-      for (int i = 0; i < TM; ++i) {
-        const int row = wm * WM + i * 16 + fr;
-        af[i] = *reinterpret_cast<const bf16x8*>(a + row * HALO_CH + ((fq ^ ((row >> 1) & 2)) << 3));
-      }
-#pragma unroll
-      for (int i = 0; i < TM; ++i)
-#pragma unroll
-        for (int j = 0; j < TN; ++j)
-          acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(af[i], bfr[j], acc[i][j], 0, 0, 0);
-      __builtin_amdgcn_s_setprio(0);
-    }
-  }
   }
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // tail re-loads drained before exit
 
@@ -1437,13 +1132,7 @@ conv_halo_k(const bf16* __restrict__ I, const bf16* __restrict__ Wp, const float
       if (co >= OC) continue;
       float v[4];
 #pragma unroll
-      for (int e = 0; e < 4; ++e) v[e] = acc[i][j][e] + cb[i][e];
-      if constexpr (RPF) {
-        if (res) {
-#pragma unroll
-          for (int e = 0; e < 4; ++e) v[e] += (float)rres[i][j][e];
-        }
-      }
+      for (int e = 0; e < 4; ++e) v[e] = acc[i][j][e] + cb[i][e];      // (acc holds the residual)
       bf16x4 o4;
 #pragma unroll
       for (int e = 0; e < 4; ++e) {
@@ -1793,168 +1482,6 @@ conv_wgrad_k(const bf16* __restrict__ dY, const bf16* __restrict__ I, float* __r
   }
 }
 
-// glds weight-gradient kernel: same GEMM and split-K as conv_wgrad_k, but
-// both operand tiles arrive global -> LDS by DMA (global_load_lds_dwordx4,
-// no VGPR staging, no ds_write pass), 64 pixels per stage, 2 stages behind a
-// counted vmcnt + raw s_barrier.  The LDS image is unpadded ([pixel][128 ch],
-// 256-B rows, lane-linear per 1-KiB DMA piece); bank conflicts of the
-// transpose reads are removed by an XOR swizzle instead of padding: logical
-// 16-B chunk c of row r lives at physical chunk c ^ 2*(r & 7) (the swizzle is
-// applied to the per-lane SOURCE address, rows 8 apart cover all 64 banks).
-template <int TAPS, int PK, int NS>
-__global__ void __launch_bounds__(256, 2)
-conv_wgrad_glds_k(const bf16* __restrict__ dY, const bf16* __restrict__ I, float* __restrict__ ws,
-                  const bf16* __restrict__ zero16, int Nimg, int IH, int IW, int IC, int OH, int OW, int OC,
-                  int stride, int pix_per_split, int ncb, float* __restrict__ bws, int lw, int lh) {
-  constexpr int BM = 128, BN = 128;
-  constexpr int WM = 64, WN = 64, TM = 4, TN = 4;
-  constexpr int STAGE = PK * (BM + BN);
-  constexpr int PPW = PK / 16;                  // 1-KiB DMA pieces per wave per operand per stage
-  __shared__ __attribute__((aligned(16))) bf16 smem[NS * STAGE];
-  typedef __attribute__((address_space(3))) void lds_void;
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int wm = wave >> 1, wn = wave & 1;
-  int bx, by, bz;
-  {
-    const int gx = gridDim.x, gy = gridDim.y;
-    const long T = (long)gx * gy * gridDim.z;
-    const long L = blockIdx.x + (long)gx * (blockIdx.y + (long)gy * blockIdx.z);
-    const long q = T / 8, r = T % 8, xcd = L % 8;
-    const long R = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + L / 8;
-    bx = (int)(R % gx);
-    by = (int)((R / gx) % gy);
-    bz = (int)(R / ((long)gx * gy));
-  }
-  const int tap = bx / ncb;
-  const int ci0 = (bx % ncb) * BN;
-  const int m0 = by * BM;
-  const int split = bz;
-  const int kh = TAPS == 9 ? tap / 3 : 1, kw = TAPS == 9 ? tap % 3 : 1;
-  const long P = (long)Nimg * OH * OW;
-  const long p_begin = (long)split * pix_per_split;
-  const long p_end = p_begin + pix_per_split < P ? p_begin + pix_per_split : P;
-  const int OHW = OH * OW;
-
-  // DMA lane mapping: wave w, piece i covers tile rows (w*PPW+i)*4 .. +3;
-  // lane L -> row +L/16, physical chunk L%16, logical chunk (L%16)^(2*(row&7))
-  const int lrow = lane >> 4, pch = lane & 15;
-  int trow[PPW], lch[PPW];
-#pragma unroll
-  for (int i = 0; i < PPW; ++i) {
-    trow[i] = (wave * PPW + i) * 4 + lrow;
-    lch[i] = pch ^ (2 * (trow[i] & 7));
-  }
-  auto issue = [&](long p0, int stage) {
-    bf16* sA = smem + stage * STAGE;
-    bf16* sB = sA + PK * BM;
-#pragma unroll
-    for (int i = 0; i < PPW; ++i) {
-      const long p = p0 + trow[i];
-      const int co = m0 + lch[i] * 8;
-      const bf16* src = (p < p_end && co < OC) ? dY + p * OC + co : zero16;
-      __builtin_amdgcn_global_load_lds((const void*)src, (lds_void*)(sA + (wave * PPW + i) * 4 * BM), 16, 0, 0);
-    }
-#pragma unroll
-    for (int i = 0; i < PPW; ++i) {
-      const long p = p0 + trow[i];
-      const int ci = ci0 + lch[i] * 8;
-      bool ok = p < p_end && ci < IC;
-      int img = 0, oh = 0, ow = 0;
-      if (lw >= 0) {
-        ow = (int)(p & (OW - 1));
-        long t = p >> lw;
-        oh = (int)(t & (OH - 1));
-        img = (int)(t >> lh);
-      } else {
-        img = (int)(p / OHW);
-        int rem = (int)(p - (long)img * OHW);
-        oh = rem / OW;
-        ow = rem - oh * OW;
-      }
-      const int ih = oh * stride + kh - 1, iw = ow * stride + kw - 1;
-      ok = ok && ih >= 0 && ih < IH && iw >= 0 && iw < IW;
-      const bf16* src = ok ? I + (((long)img * IH + ih) * IW + iw) * IC + ci : zero16;
-      __builtin_amdgcn_global_load_lds((const void*)src, (lds_void*)(sB + (wave * PPW + i) * 4 * BN), 16, 0, 0);
-    }
-  };
-  auto sw = [](int row, int col) { return row * 128 + ((((col >> 3) ^ (2 * (row & 7)))) << 3) + (col & 7); };
-
-  f32x4 acc[TM][TN];
-#pragma unroll
-  for (int i = 0; i < TM; ++i)
-#pragma unroll
-    for (int j = 0; j < TN; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
-
-  const int g = lane >> 4, q = (lane & 15) >> 2, pc = lane & 3;
-  const long nsteps = (p_end - p_begin + PK - 1) / PK;
-  const bool do_bias = bws != nullptr && bx == 0;
-  float bacc = 0.f;
-#pragma unroll
-  for (int k = 0; k < NS - 1; ++k)
-    if (k < nsteps) issue(p_begin + k * PK, k);
-  for (long s = 0; s < nsteps; ++s) {
-    const int st = (int)(s % NS);
-    // retire stage s; the (up to NS-2) stages issued after it stay in flight
-    if (NS == 3 && s + 1 < nsteps) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(2 * PPW) : "memory");
-    else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __builtin_amdgcn_s_barrier();          // stage s visible; stage s-1 fully read by every wave
-    if (s + NS - 1 < nsteps) issue(p_begin + (s + NS - 1) * PK, (int)((s + NS - 1) % NS));
-    const bf16* a = smem + st * STAGE;
-    const bf16* b = a + PK * BM;
-    if (do_bias) {
-      const int col = tid & 127, r0 = (tid >> 7) * (PK / 2);
-#pragma unroll 8
-      for (int r = 0; r < PK / 2; ++r) bacc += (float)a[sw(r0 + r, col)];
-    }
-#pragma unroll
-    for (int kk = 0; kk < PK / 32; ++kk) {
-      const int r1 = kk * 32 + 4 * g + q, r2 = r1 + 16;
-      bf16x8 af[TM], bfr[TN];
-#pragma unroll
-      for (int i = 0; i < TM; ++i) {
-        const int col = wm * WM + i * 16 + 4 * pc;
-        s16x4 lo = ds_tr(a + sw(r1, col));
-        s16x4 hi = ds_tr(a + sw(r2, col));
-        s16x8 v = {lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
-        af[i] = __builtin_bit_cast(bf16x8, v);
-      }
-#pragma unroll
-      for (int j = 0; j < TN; ++j) {
-        const int col = wn * WN + j * 16 + 4 * pc;
-        s16x4 lo = ds_tr(b + sw(r1, col));
-        s16x4 hi = ds_tr(b + sw(r2, col));
-        s16x8 v = {lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
-        bfr[j] = __builtin_bit_cast(bf16x8, v);
-      }
-#pragma unroll
-      for (int i = 0; i < TM; ++i)
-#pragma unroll
-        for (int j = 0; j < TN; ++j)
-          acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(af[i], bfr[j], acc[i][j], 0, 0, 0);
-    }
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");   // reads retired before the next top barrier
-  }
-  if (do_bias) {
-    const int col = tid & 127, half = tid >> 7;
-    if (m0 + col < OC) bws[((long)split * 2 + half) * OC + m0 + col] = bacc;
-  }
-  const int fr = lane & 15, fq = lane >> 4;
-  const long KW = (long)TAPS * IC;
-  float* slab = ws + (long)split * OC * KW;
-#pragma unroll
-  for (int j = 0; j < TN; ++j) {
-    int ci = ci0 + wn * WN + j * 16 + fr;
-    if (ci >= IC) continue;
-#pragma unroll
-    for (int i = 0; i < TM; ++i) {
-      int co = m0 + wm * WM + i * 16 + fq * 4;
-#pragma unroll
-      for (int e = 0; e < 4; ++e)
-        if (co + e < OC) slab[(long)(co + e) * KW + tap * IC + ci] = acc[i][j][e];
-    }
-  }
-}
-
 // Buffer descriptor whose inputs are forced wave-uniform (readfirstlane):
 // hipcc cannot always prove uniformity of values derived through loops and
 // would otherwise wrap every buffer op in a waterfall loop (guide T20).
@@ -2030,9 +1557,15 @@ __device__ __forceinline__ void wgrad_bufl_issue(bf16* sA, bf16* sB, const bf16*
   }
 }
 
-// Buffer-descriptor LDS-DMA weight-gradient kernel.  Same GEMM, split-K,
-// swizzled unpadded LDS image and transpose reads as conv_wgrad_glds_k, with
-// the VALU-issue bottleneck of the flat-address loaders removed:
+// Buffer-descriptor LDS-DMA weight-gradient kernel.  Same GEMM and split-K as
+// conv_wgrad_k, but both operand tiles arrive global -> LDS by DMA (no VGPR
+// staging, no ds_write pass), PK pixels per stage, 2 stages.  The LDS image is
+// unpadded ([pixel][128 ch], 256-B rows, lane-linear per 1-KiB DMA piece);
+// bank conflicts of the transpose reads are removed by an XOR swizzle instead
+// of padding: logical 16-B chunk c of row r lives at physical chunk
+// c ^ 2*(r & 7) (the swizzle is applied to the per-lane SOURCE address, rows 8
+// apart cover all 64 banks).  Against flat-address loaders, which were bound
+// by VALU issue:
 //  * operand descriptors are re-based per stage with scalar math (the pixel
 //    window advances by PK), so per-lane offsets are loop-invariant;
 //  * the dY descriptor's record count ends at this split's last pixel and
@@ -2919,11 +2452,6 @@ static bool s64_wanted(long Mpix, int OC, int ICp, int taps) {
   const long blocks64 = ((Mpix + 63) / 64) * (OC / 64);
   return g_s64 && OC % 64 == 0 && (taps * ICp) % 64 == 0 && blocks128 <= g_s64_maxb && blocks64 >= 128;
 }
-// 1: the residual-free convs (dgrad, conv1) still run the residual-capable
-// kernel variants (round-3 behaviour; A/B switch for the RES template)
-static int g_conv_res_always = 0;
-// conv_halo_k AU (unrolled taps, precomputed B offsets, residual preloaded into the accumulators); 0 off
-static int g_halo_au = 1;
 // 32-wide images on the halo kernel (16-row tiles) when the grid fills the chip:
 // the 32x32 level at bs128 903 -> 1020 TF/s fwd, 892 -> 979 dgrad against
 // conv_w8_k (profiles/r4/halo_w32/)
@@ -2935,37 +2463,55 @@ static int g_halo_w32 = 1;
 static int g_halo_w16 = 1;
 static int g_halo_w32s = 1;
 static int g_halo_p2 = 1;          // tap pairs per barrier (8-slot weight ring) on the 512-pixel tiles
-// knob: bits 0-1 AU (0 off / 1 on), bit 2 the 32-wide halo, bit 3 the 16-wide halo, bit 4 the 8-row
-// 32-wide tiles, bit 5 tap pairs per barrier (D3D_HALO_AU=61: all, the default; 29: all but
-// the tap pairs -- profiles/r4/halo_p2: fwd -2..4 % on the N=256 levels, bs128 +0.7 %, bs16 +0.3 %)
-D3D_API int d3d_conv_halo_cfg(int au) {
-  g_halo_au = au & 3;
-  g_halo_w32 = (au >> 2) & 1;
-  g_halo_w16 = (au >> 3) & 1;
-  g_halo_w32s = (au >> 4) & 1;
-  g_halo_p2 = (au >> 5) & 1;
+// knob (D3D_HALO_AU): bit 2 the 32-wide halo, bit 3 the 16-wide halo, bit 4 the 8-row 32-wide
+// tiles, bit 5 tap pairs per barrier (61 or 60: all, the default; 28: all but the tap pairs --
+// profiles/r4/halo_p2: fwd -2..4 % on the N=256 levels, bs128 +0.7 %, bs16 +0.3 %).  Bits 0-1
+// once chose the tap schedule; the unrolled one is the only one left and they are ignored.
+D3D_API int d3d_conv_halo_cfg(int cfg) {
+  g_halo_w32 = (cfg >> 2) & 1;
+  g_halo_w16 = (cfg >> 3) & 1;
+  g_halo_w32s = (cfg >> 4) & 1;
+  g_halo_p2 = (cfg >> 5) & 1;
   return 0;
 }
-D3D_API int d3d_conv_res_cfg(int always) {
-  g_conv_res_always = always;
-  return 0;
-}
-static int g_conv_impl = -1;      // 0: register-staged, 1: glds pipeline, 2: buffer-descriptor LDS-DMA
-static int g_conv_korder = 1;     // glds k-step order: 1 channel-chunk major, 0 tap major
-static int g_wgrad_impl = 5;      // 0: register-staged; 1-4: glds (PK,NS) = (64,2) (32,2) (32,3) (64,3); 5: bufl
-static const bf16* g_zero16 = nullptr;
+
+// Kernel ceilings (hip_impl.set_conv_impl / set_wgrad_impl pass these values
+// by name).  A ceiling is the most specialised kernel the dispatcher may pick;
+// a shape the ceiling's kernel does not take falls down the ladder:
+//   forward / dgrad (d3d_conv3): conv_halo_k -> conv_small.hip (small grids, at
+//     every ceiling) -> conv_w8_k -> conv_bufl_k -> conv_glds_k (catch-all);
+//   weight gradient (launch_wgrad, wgrad_w8_ok): conv_wgrad_w8_k ->
+//     conv_wgrad_bufl_k -> conv_wgrad_k (catch-all).
+// The numbers are those of the longer ladders this one was cut from, so a
+// library built from an older revision reads them the same way.
+enum ConvImpl {
+  CONV_BUFL = 3,   // "bufl": conv_bufl_k, 128 x 128 tiles (split-K on small grids)
+  CONV_W8 = 4,     // "w8":   + conv_w8_k 256 x 256 tiles where they fill the chip
+  CONV_W8W = 6,    // "w8w":  + its 128 x 512 tiles for 128 / 384-channel layers
+  CONV_W8N = 7,    // "w8n":  + its 256 x 128 tiles where 256 x 256 ones leave CUs idle
+  CONV_HALO = 8,   // "halo": w8w + conv_halo_k on stride-1 3x3 convs (the default)
+};
+enum WgradImpl {
+  WGRAD_REG = 0,   // "reg":  conv_wgrad_k only
+  WGRAD_BUFL = 5,  // "bufl": + conv_wgrad_bufl_k
+  WGRAD_W8 = 6,    // "w8":   + conv_wgrad_w8_k (the default)
+};
+static int g_conv_impl = CONV_HALO;
+static int g_wgrad_impl = WGRAD_W8;
+static const bf16* g_zero16 = nullptr;   // 16 zero bytes on the device: conv_glds_k's padding source
+// k-step order of the implicit-GEMM kernels: channel-chunk major (the
+// tap-major order, 0, is no longer selectable)
+static const int kConvKorder = 1;
 
 D3D_API int d3d_set_wgrad_impl(int impl) {
+  if (impl != WGRAD_REG && impl != WGRAD_BUFL && impl != WGRAD_W8) return (int)hipErrorInvalidValue;
   g_wgrad_impl = impl;
   return 0;
 }
 
-D3D_API int d3d_set_conv_korder(int korder) {
-  g_conv_korder = korder;
-  return 0;
-}
-
 D3D_API int d3d_set_conv_impl(int impl, const void* zero16) {
+  if (impl != CONV_BUFL && impl != CONV_W8 && impl != CONV_W8W && impl != CONV_W8N && impl != CONV_HALO)
+    return (int)hipErrorInvalidValue;
   g_conv_impl = impl;
   if (zero16) g_zero16 = (const bf16*)zero16;
   return 0;
@@ -2981,8 +2527,8 @@ D3D_API int d3d_conv_plan(int N, int OH, int OW, int OC, int ICp, int taps) {
   long blocks = ((Mpix + BN - 1) / BN) * ((OC + BM - 1) / BM);
   int nk = taps * ICp / 64;
   static const int target = 512;
-  if (blocks >= 384 || (OC & 3) || g_conv_impl < 1) return 1;
-  if (g_conv_impl >= 2 && s64_wanted(Mpix, OC, ICp, taps)) return 1;     // no-split small tiles instead
+  if (blocks >= 384 || (OC & 3)) return 1;
+  if (s64_wanted(Mpix, OC, ICp, taps)) return 1;     // no-split small tiles instead
   long want = target / blocks;      // rounded down: no nearly empty extra round of blocks
   long maxs = nk / 6;
   if (want > maxs) want = maxs;
@@ -3008,7 +2554,7 @@ D3D_API int d3d_conv3(const void* I, const void* Wp, const float* bias, const fl
   // Operands beyond the kernels' 32-bit buffer offsets (2 GiB: e.g. the
   // 256-channel decoder concat of 128x128 images at one micro-batch of 128):
   // run the conv over image chunks that fit, each at full speed, instead of
-  // dropping to the register-staged fallback.  Chunk boundaries are multiples
+  // dropping to the flat-address catch-all.  Chunk boundaries are multiples
   // of res_nmod (the broadcast residual's period); per-image operands
   // (output, per-image bias rows, GroupNorm partial slots) are offset, the
   // split-K workspace is reused chunk after chunk on the stream.
@@ -3050,8 +2596,8 @@ D3D_API int d3d_conv3(const void* I, const void* Wp, const float* bias, const fl
     if (!ok) gnp = nullptr;
   }
   constexpr int BM = 128, BN = 128;
-  if (nsplit < 1 || !ws || g_conv_impl < 1) nsplit = 1;
-  if (g_conv_impl >= 2 && nsplit == 1 && s64_wanted(Mpix, OC, ICp, taps)) {
+  if (nsplit < 1 || !ws) nsplit = 1;
+  if (nsplit == 1 && s64_wanted(Mpix, OC, ICp, taps)) {
     const int rh = d3d_conv_hsm_try(I, Wp, bias, row_bias, res, O, N, IH, IW, IC, ICp, OH, OW, OC, ldo, stride, trans,
                                     scale, res_nmod, taps, gnp, O2, st);
     if (rh != 0) return rh < 0 ? -rh : 0;
@@ -3062,36 +2608,33 @@ D3D_API int d3d_conv3(const void* I, const void* Wp, const float* bias, const fl
   }
   dim3 grid((unsigned)((Mpix + BN - 1) / BN), (unsigned)((OC + BM - 1) / BM), (unsigned)nsplit);
   const long in_bytes = (long)N * IH * IW * IC * 2, w_bytes = (long)((OC + 127) / 128 * 128) * taps * ICp * 2;
-  if (g_conv_impl == 8 && taps == 9 && stride == 1 && IW == OW && IH == OH && ldo == OC && IC % HALO_CH == 0 &&
+  if (g_conv_impl == CONV_HALO && taps == 9 && stride == 1 && IW == OW && IH == OH && ldo == OC && IC % HALO_CH == 0 &&
       OC % 128 == 0 && (OW == 16 || OW == 32 || OW == 64 || OW == 128) && in_bytes < (1L << 31) &&
       w_bytes < (1L << 31)) {
     // 512-pixel tiles where they fill the chip (64/128-wide images)
     auto nblk = [&](int bn) { return OH % (bn / OW) ? 0L : (long)N * (OH / (bn / OW)) * (OC / 128); };
     if ((OW != 32 || g_halo_w32) && nblk(512) >= 256) {
       dim3 gh((unsigned)(N * (OH / (512 / OW))), (unsigned)(OC / 128), 1);
-#define HALO3(OWv, TR, RS, AUv, P2v)                                                                              \
-  hipLaunchKernelGGL((conv_halo_k<OWv, TR, 512, false, RS, AUv, (P2v && OWv != 128)>), gh, dim3(512), 0, st, (const bf16*)I,     \
+#define HALO3(OWv, TR, RS, P2v)                                                                                   \
+  hipLaunchKernelGGL((conv_halo_k<OWv, TR, 512, RS, (P2v && OWv != 128)>), gh, dim3(512), 0, st, (const bf16*)I,  \
                      (const bf16*)Wp, bias, row_bias, (const bf16*)res, (bf16*)O, (int)in_bytes, (int)w_bytes, N, OH, \
                      IC, ICp, OC, scale, res_nmod, gnp, gn_groups, (bf16*)O2, (const float*)nullptr)
-#define HALO2(OWv, TR, RS, AUv) HALO3(OWv, TR, RS, AUv, false)
 #define HALO(OWv, TR, RS)                                                                                          \
   do {                                                                                                            \
-    if (g_halo_au && g_halo_p2 && OWv != 128 && (IC / HALO_CH) % 2 == 0) HALO3(OWv, TR, RS, true, true);          \
-    else if (g_halo_au) HALO2(OWv, TR, RS, true);                                                                   \
-    else HALO2(OWv, TR, RS, false);                                                                                 \
+    if (g_halo_p2 && OWv != 128 && (IC / HALO_CH) % 2 == 0) HALO3(OWv, TR, RS, true);                             \
+    else HALO3(OWv, TR, RS, false);                                                                               \
   } while (0)
       if (OW == 64) {
-        if (trans) { if (res || g_conv_res_always) HALO(64, true, true); else HALO(64, true, false); }
-        else if (res || g_conv_res_always) HALO(64, false, true); else HALO(64, false, false);
+        if (trans) { if (res) HALO(64, true, true); else HALO(64, true, false); }
+        else if (res) HALO(64, false, true); else HALO(64, false, false);
       } else if (OW == 32) {
-        if (trans) { if (res || g_conv_res_always) HALO(32, true, true); else HALO(32, true, false); }
-        else if (res || g_conv_res_always) HALO(32, false, true); else HALO(32, false, false);
+        if (trans) { if (res) HALO(32, true, true); else HALO(32, true, false); }
+        else if (res) HALO(32, false, true); else HALO(32, false, false);
       } else {
-        if (trans) { if (res || g_conv_res_always) HALO(128, true, true); else HALO(128, true, false); }
-        else if (res || g_conv_res_always) HALO(128, false, true); else HALO(128, false, false);
+        if (trans) { if (res) HALO(128, true, true); else HALO(128, true, false); }
+        else if (res) HALO(128, false, true); else HALO(128, false, false);
       }
 #undef HALO
-#undef HALO2
 #undef HALO3
       if (gn_done && gnp) *gn_done = 1;
       if (silu_done && O2) *silu_done = 1;
@@ -3102,15 +2645,15 @@ D3D_API int d3d_conv3(const void* I, const void* Wp, const float* bias, const fl
       // 32-wide one where the 16-row tiles would not fill the chip (bs16)
       dim3 gh((unsigned)(N * (OH / (256 / OW))), (unsigned)(OC / 128), 1);
 #define HALOS(OWv, TR, RS)                                                                                         \
-  hipLaunchKernelGGL((conv_halo_k<OWv, TR, 256, false, RS, true>), gh, dim3(512), 0, st, (const bf16*)I,           \
+  hipLaunchKernelGGL((conv_halo_k<OWv, TR, 256, RS>), gh, dim3(512), 0, st, (const bf16*)I,                        \
                      (const bf16*)Wp, bias, row_bias, (const bf16*)res, (bf16*)O, (int)in_bytes, (int)w_bytes, N, OH, \
                      IC, ICp, OC, scale, res_nmod, gnp, gn_groups, (bf16*)O2, (const float*)nullptr)
       if (OW == 16) {
-        if (trans) { if (res || g_conv_res_always) HALOS(16, true, true); else HALOS(16, true, false); }
-        else if (res || g_conv_res_always) HALOS(16, false, true); else HALOS(16, false, false);
+        if (trans) { if (res) HALOS(16, true, true); else HALOS(16, true, false); }
+        else if (res) HALOS(16, false, true); else HALOS(16, false, false);
       } else {
-        if (trans) { if (res || g_conv_res_always) HALOS(32, true, true); else HALOS(32, true, false); }
-        else if (res || g_conv_res_always) HALOS(32, false, true); else HALOS(32, false, false);
+        if (trans) { if (res) HALOS(32, true, true); else HALOS(32, true, false); }
+        else if (res) HALOS(32, false, true); else HALOS(32, false, false);
       }
 #undef HALOS
       if (gn_done && gnp) *gn_done = 1;
@@ -3118,18 +2661,18 @@ D3D_API int d3d_conv3(const void* I, const void* Wp, const float* bias, const fl
       return (int)hipGetLastError();
     }
   }
-  if (g_conv_impl >= 4 && (!trans || stride == 1) && in_bytes < (1L << 31) && w_bytes < (1L << 31) && OC >= 64) {
+  if (g_conv_impl >= CONV_W8 && (!trans || stride == 1) && in_bytes < (1L << 31) && w_bytes < (1L << 31) && OC >= 64) {
     // large-tile 8-wave kernel when its grid still covers every CU
     const int bm = (OC % 256 == 0 || OC > 384) ? 256 : 128;
-    // 128 / 384-channel layers only as 128x512 tiles on request (impl 6):
-    // 128x256 tiles measured slower than two 128x128 blocks per CU (bufl1)
-    const bool wide = bm == 128 && g_conv_impl >= 6;         // w8w, w8n, halo
+    // 128 / 384-channel layers only as 128x512 tiles, from CONV_W8W up:
+    // 128x256 tiles measured slower than two 128x128 blocks per CU (conv_bufl_k)
+    const bool wide = bm == 128 && g_conv_impl >= CONV_W8W;  // w8w, w8n, halo
     int bn = wide ? 512 : 256;
     long ptiles = (Mpix + bn - 1) / bn;
     long blocks = ptiles * ((OC + bm - 1) / bm);
-    // impl 7: 256 x 128 tiles when 256 x 256 ones would leave CUs idle but
+    // CONV_W8N: 256 x 128 tiles when 256 x 256 ones would leave CUs idle but
     // the narrower tile still gives every CU a block
-    if (g_conv_impl == 7 && bm == 256 && blocks < 256 && ((Mpix + 127) / 128) * ((OC + 255) / 256) >= 256) {
+    if (g_conv_impl == CONV_W8N && bm == 256 && blocks < 256 && ((Mpix + 127) / 128) * ((OC + 255) / 256) >= 256) {
       bn = 128;
       ptiles = (Mpix + bn - 1) / bn;
       blocks = ptiles * ((OC + bm - 1) / bm);
@@ -3139,10 +2682,10 @@ D3D_API int d3d_conv3(const void* I, const void* Wp, const float* bias, const fl
 #define W8R(TP, TR, BMv, BNv, RS)                                                                                \
   hipLaunchKernelGGL((conv_w8_k<TP, TR, BMv, BNv, RS>), g8, dim3(512), 0, st, (const bf16*)I, (const bf16*)Wp, bias, \
                      row_bias, (const bf16*)res, (bf16*)O, (int)in_bytes, (int)w_bytes, N, IH, IW, IC, ICp, OH, OW, \
-                     OC, ldo, stride, scale, res_nmod, g_conv_korder, gnp, gn_groups, (bf16*)O2)
+                     OC, ldo, stride, scale, res_nmod, kConvKorder, gnp, gn_groups, (bf16*)O2)
 #define W8(TP, TR, BMv, BNv)                                                                                     \
   do {                                                                                                          \
-    if (res || g_conv_res_always) W8R(TP, TR, BMv, BNv, true); else W8R(TP, TR, BMv, BNv, false);               \
+    if (res) W8R(TP, TR, BMv, BNv, true); else W8R(TP, TR, BMv, BNv, false);                                     \
   } while (0)
       if (bn == 128) {
         if (taps == 9) {
@@ -3170,25 +2713,17 @@ D3D_API int d3d_conv3(const void* I, const void* Wp, const float* bias, const fl
       return (int)hipGetLastError();
     }
   }
-  if (g_conv_impl >= 2 && (!trans || stride == 1) && in_bytes < (1L << 31) && w_bytes < (1L << 31)) {
+  if ((!trans || stride == 1) && in_bytes < (1L << 31) && w_bytes < (1L << 31)) {
     float* part = nsplit > 1 ? ws : nullptr;
-#define BUFL(TP, TR, OB)                                                                                         \
-  hipLaunchKernelGGL((conv_bufl_k<TP, TR, OB>), grid, dim3(256), 0, st, (const bf16*)I, (const bf16*)Wp, bias,    \
+#define BUFL(TP, TR)                                                                                             \
+  hipLaunchKernelGGL((conv_bufl_k<TP, TR>), grid, dim3(256), 0, st, (const bf16*)I, (const bf16*)Wp, bias,        \
                      row_bias, (const bf16*)res, (bf16*)O, (int)in_bytes, (int)w_bytes, N, IH, IW, IC, ICp, OH, OW, \
-                     OC, ldo, stride, scale, res_nmod, part, g_conv_korder, part ? nullptr : gnp, gn_groups,       \
+                     OC, ldo, stride, scale, res_nmod, part, kConvKorder, part ? nullptr : gnp, gn_groups,         \
                      part ? nullptr : (bf16*)O2)
-    if (g_conv_impl >= 3) {
-      if (taps == 9) {
-        if (trans) BUFL(9, true, true); else BUFL(9, false, true);
-      } else {
-        if (trans) BUFL(1, true, true); else BUFL(1, false, true);
-      }
+    if (taps == 9) {
+      if (trans) BUFL(9, true); else BUFL(9, false);
     } else {
-      if (taps == 9) {
-        if (trans) BUFL(9, true, false); else BUFL(9, false, false);
-      } else {
-        if (trans) BUFL(1, true, false); else BUFL(1, false, false);
-      }
+      if (trans) BUFL(1, true); else BUFL(1, false);
     }
 #undef BUFL
     if (part && gnp && OC % 64 == 0) {
@@ -3209,37 +2744,28 @@ D3D_API int d3d_conv3(const void* I, const void* Wp, const float* bias, const fl
     if (silu_done && O2) *silu_done = 1;
     return (int)hipGetLastError();
   }
-  if (g_conv_impl >= 1 && g_zero16) {
-    float* part = nsplit > 1 ? ws : nullptr;
+  // catch-all: flat addresses (transposed convs with stride > 1, operands
+  // past 2 GiB that the chunking above could not split); padding reads come
+  // from the zero page d3d_set_conv_impl was given
+  if (!g_zero16) return (int)hipErrorInvalidValue;
+  float* part = nsplit > 1 ? ws : nullptr;
 #define GLDS(TP, TR)                                                                                             \
   hipLaunchKernelGGL((conv_glds_k<TP, TR>), grid, dim3(256), 0, st, (const bf16*)I, (const bf16*)Wp, bias,        \
                      row_bias, (const bf16*)res, (bf16*)O, g_zero16, N, IH, IW, IC, ICp, OH, OW, OC, ldo, stride, \
-                     scale, res_nmod, part, g_conv_korder)
-    if (taps == 9) {
-      if (trans) GLDS(9, true); else GLDS(9, false);
-    } else {
-      if (trans) GLDS(1, true); else GLDS(1, false);
-    }
-#undef GLDS
-    if (part) {
-      long nv = Mpix * (OC / 4);
-      long g = (nv + 255) / 256;
-      if (g > 4096) g = 4096;
-      hipLaunchKernelGGL(conv_splitk_epi_k, dim3((unsigned)g), dim3(256), 0, st, part, nsplit, Mpix, OC, OH * OW,
-                         bias, row_bias, (const bf16*)res, res_nmod, (bf16*)O, ldo, scale, (bf16*)nullptr);
-    }
-    return (int)hipGetLastError();
-  }
-#define LAUNCH(TR, TP)                                                                                             \
-  hipLaunchKernelGGL((conv_igemm_k<BM, BN, TR, TP>), grid, dim3(256), 0, st, (const bf16*)I, (const bf16*)Wp, bias, \
-                     row_bias, (const bf16*)res, (bf16*)O, N, IH, IW, IC, ICp, OH, OW, OC, ldo, stride, scale,      \
-                     res_nmod)
+                     scale, res_nmod, part, kConvKorder)
   if (taps == 9) {
-    if (trans) LAUNCH(true, 9); else LAUNCH(false, 9);
+    if (trans) GLDS(9, true); else GLDS(9, false);
   } else {
-    if (trans) LAUNCH(true, 1); else LAUNCH(false, 1);
+    if (trans) GLDS(1, true); else GLDS(1, false);
   }
-#undef LAUNCH
+#undef GLDS
+  if (part) {
+    long nv = Mpix * (OC / 4);
+    long g = (nv + 255) / 256;
+    if (g > 4096) g = 4096;
+    hipLaunchKernelGGL(conv_splitk_epi_k, dim3((unsigned)g), dim3(256), 0, st, part, nsplit, Mpix, OC, OH * OW,
+                       bias, row_bias, (const bf16*)res, res_nmod, (bf16*)O, ldo, scale, (bf16*)nullptr);
+  }
   return (int)hipGetLastError();
 }
 
@@ -3250,7 +2776,7 @@ D3D_API int d3d_conv3(const void* I, const void* Wp, const float* bias, const fl
 // another kernel, so the caller keeps the separate GroupNorm pass.
 static int conv3_gn_shape(int N, int H, int W, int IC, int OC, int* tile) {
   const long in_bytes = (long)N * H * W * IC * 2, w_bytes = (long)((OC + 127) / 128 * 128) * 9 * ((IC + 63) / 64 * 64) * 2;
-  if (g_conv_impl != 8 || !g_halo_au || IC % HALO_CH || OC % 128 || (W != 32 && W != 64) || in_bytes >= (1L << 31) ||
+  if (g_conv_impl != CONV_HALO || IC % HALO_CH || OC % 128 || (W != 32 && W != 64) || in_bytes >= (1L << 31) ||
       w_bytes >= (1L << 31) || IC > 512)
     return 0;
   auto nblk = [&](int bn) { return H % (bn / W) ? 0L : (long)N * (H / (bn / W)) * (OC / 128); };
@@ -3282,37 +2808,12 @@ D3D_API int d3d_conv3_gn(const void* I, const void* Wp, const float* bias, void*
   }
   const long in_bytes = (long)N * H * W * IC * 2, w_bytes = (long)((OC + 127) / 128 * 128) * 9 * ICp * 2;
   dim3 gh((unsigned)(N * (H / (tile / W))), (unsigned)(OC / 128), 1);
-#define GNL(OWv, BNv, P2v)                                                                                          \
-  hipLaunchKernelGGL((conv_halo_k<OWv, false, BNv, false, false, true, P2v, true>), gh, dim3(512), 0, st,            \
-                     (const bf16*)I, (const bf16*)Wp, bias, (const float*)nullptr, (const bf16*)nullptr, (bf16*)O,    \
-                     (int)in_bytes, (int)w_bytes, N, H, IC, ICp, OC, 1.f, 0, gnp, gn_groups, (bf16*)nullptr, gab)
-  GNL(32, 256, false);
-  (void)tile;
-#undef GNL
+  // <OWT 32, forward, 256-pixel tile, no residual, single taps, GNA>: the one tile conv3_gn_shape accepts
+  hipLaunchKernelGGL((conv_halo_k<32, false, 256, false, false, true>), gh, dim3(512), 0, st, (const bf16*)I,
+                     (const bf16*)Wp, bias, (const float*)nullptr, (const bf16*)nullptr, (bf16*)O, (int)in_bytes,
+                     (int)w_bytes, N, H, IC, ICp, OC, 1.f, 0, gnp, gn_groups, (bf16*)nullptr, gab);
   if (gn_done && gnp) *gn_done = 1;
   return (int)hipGetLastError();
-}
-
-D3D_API int d3d_conv2(const void* I, const void* Wp, const float* bias, const float* row_bias, const void* res,
-                      void* O, int N, int IH, int IW, int IC, int ICp, int OH, int OW, int OC, int ldo, int stride,
-                      int trans, float scale, int res_nmod, int taps, float* ws, int nsplit, float* gnp,
-                      int gn_groups, int* gn_done, hipStream_t st) {
-  return d3d_conv3(I, Wp, bias, row_bias, res, O, N, IH, IW, IC, ICp, OH, OW, OC, ldo, stride, trans, scale,
-                   res_nmod, taps, ws, nsplit, gnp, gn_groups, gn_done, nullptr, nullptr, st);
-}
-
-D3D_API int d3d_conv(const void* I, const void* Wp, const float* bias, const float* row_bias, const void* res,
-                     void* O, int N, int IH, int IW, int IC, int ICp, int OH, int OW, int OC, int ldo, int stride,
-                     int trans, float scale, int res_nmod, int taps, float* ws, int nsplit, hipStream_t st) {
-  return d3d_conv2(I, Wp, bias, row_bias, res, O, N, IH, IW, IC, ICp, OH, OW, OC, ldo, stride, trans, scale,
-                   res_nmod, taps, ws, nsplit, nullptr, 0, nullptr, st);
-}
-
-D3D_API int d3d_conv3x3(const void* I, const void* Wp, const float* bias, const float* row_bias, const void* res,
-                        void* O, int N, int IH, int IW, int IC, int ICp, int OH, int OW, int OC, int ldo,
-                        int stride, int trans, float scale, int res_nmod, hipStream_t st) {
-  return d3d_conv(I, Wp, bias, row_bias, res, O, N, IH, IW, IC, ICp, OH, OW, OC, ldo, stride, trans, scale,
-                  res_nmod, 9, nullptr, 1, st);
 }
 
 // launches wgrad_reduce2_k<SL> with SL = splits rounded up to a power of two
@@ -3366,7 +2867,7 @@ static void launch_wgrad(const void* dY, const void* I, float* ws, int N, int IH
   // keep it to full 128-channel tiles).  FAST re-bases the input descriptor
   // per stage, so only the general path is bounded by 32-bit input offsets.
   const bool fast = stride == 1 && lw >= 0 && IH == OH && IW == OW && IC % 128 == 0;
-  if (g_wgrad_impl >= 5 && !wide_long && (fast || in_elems * 2 < (1L << 31) - (1L << 20)) &&
+  if (g_wgrad_impl >= WGRAD_BUFL && !wide_long && (fast || in_elems * 2 < (1L << 31) - (1L << 20)) &&
       (long)pps * OC * 2 < (1L << 31)) {
     constexpr int PK = 32;
 #define WB(TP, F)                                                                                                \
@@ -3386,21 +2887,7 @@ static void launch_wgrad(const void* dY, const void* I, float* ws, int N, int IH
 #undef WB
     return;
   }
-  if (g_wgrad_impl >= 1 && g_wgrad_impl <= 4 && g_zero16) {
-#define WG(TP, PKv, NSv)                                                                                         \
-  hipLaunchKernelGGL((conv_wgrad_glds_k<TP, PKv, NSv>), grid, dim3(256), 0, st, (const bf16*)dY, (const bf16*)I, ws, \
-                     g_zero16, N, IH, IW, IC, OH, OW, OC, stride, pps, ncb, bws, lw, lh)
-#define WGT(PKv, NSv) do { if (taps == 9) WG(9, PKv, NSv); else WG(1, PKv, NSv); } while (0)
-    switch (g_wgrad_impl) {
-      case 2: WGT(32, 2); break;
-      case 3: WGT(32, 3); break;
-      case 4: WGT(64, 3); break;
-      default: WGT(64, 2); break;
-    }
-#undef WGT
-#undef WG
-    return;
-  }
+  // catch-all (64-bit addresses, any geometry): WGRAD_REG, wide_long, inputs past 2 GiB off the FAST path
   if (taps == 9)
     hipLaunchKernelGGL((conv_wgrad_k<BM, BN, 9>), grid, dim3(256), 0, st, (const bf16*)dY, (const bf16*)I, ws, N, IH,
                        IW, IC, OH, OW, OC, stride, pps, ncb, bws, lw, lh);
@@ -3433,7 +2920,7 @@ D3D_API int d3d_conv_wgrad_plan2(int N, int OH, int OW, int OC, int IC, int taps
 
 // conv_wgrad_w8_k takes a 3x3 stride-1 same-size power-of-two shape when
 // at least one of its channel counts fills a 256-wide tile side (the 128x128
-// level-0 convs stay on the 4-wave kernel); impl 6 enables it.
+// level-0 convs stay on the 4-wave kernel); WGRAD_W8 enables it.
 // taps == 1 (per-pixel GEMMs): any geometry,
 // long reductions (the FiLM projections over every pixel of a level) are
 // where the 4-wave kernel's 16-MFMA stages stall most.
@@ -3446,7 +2933,7 @@ static bool wgrad_w8_ok(int taps, int IH, int IW, int OH, int OW, int IC, int OC
                         int* bn) {
   auto pow2 = [](int v) { return v > 0 && (v & (v - 1)) == 0; };
   // (the input descriptor is re-based per stage: no bound on the input size)
-  if (g_wgrad_impl != 6 || IC % 128 || OC % 8) return false;
+  if (g_wgrad_impl != WGRAD_W8 || IC % 128 || OC % 8) return false;
   if (taps == 1) {
     if (!wgrad_w8_1x1() || stride != 1 || IH != OH || IW != OW) return false;
   } else if (taps != 9 || stride != 1 || IH != OH || IW != OW || !pow2(OH) || !pow2(OW)) {
@@ -3508,16 +2995,13 @@ static void launch_wgrad_w8(const void* dY, const void* I, float* ws, int N, int
 #undef WW
 }
 
-D3D_API int d3d_conv_wgrad_plan(int N, int OH, int OW, int OC, int IC, int* splits, int* pix_per_split) {
-  return d3d_conv_wgrad_plan2(N, OH, OW, OC, IC, 9, splits, pix_per_split);
-}
-
 // dY: [N, OH, OW, OC] bf16 (OC % 8 == 0); I: [N, IH, IW, IC] bf16.
-// ws: [splits][OC][taps*IC] fp32 workspace.  dW: [OC][IC][taps] fp32 (OIHW).
+// dW: [OC][IC][taps] fp32 (OIHW).
 // ws: [splits][OC][taps*IC] + (db ? 2*splits*OC : 0) fp32 workspace.
 // dW (and db when non-null) are written (accumulate=0) or added to
 // (accumulate=1) -- the latter lets kernels deposit straight into the flat
-// gradient buffer across micro-batches.
+// gradient buffer across micro-batches.  They are the gradients of the conv
+// whose output gradient is scale * dY (scale folded into the split reduction).
 D3D_API int d3d_conv_wgrad3(const void* dY, const void* I, float* ws, float* dW, float* db, int N, int IH, int IW,
                             int IC, int OH, int OW, int OC, int stride, int splits, int pix_per_split, int accumulate,
                             int taps, float scale, hipStream_t st) {
@@ -3543,15 +3027,6 @@ D3D_API int d3d_conv_wgrad3(const void* dY, const void* I, float* ws, float* dW,
   return (int)hipGetLastError();
 }
 
-// dW (+ db) of the conv whose output gradient is scale * dY (scale folded
-// into the split reduction)
-D3D_API int d3d_conv_wgrad2(const void* dY, const void* I, float* ws, float* dW, float* db, int N, int IH, int IW,
-                            int IC, int OH, int OW, int OC, int stride, int splits, int pix_per_split, int accumulate,
-                            int taps, hipStream_t st) {
-  return d3d_conv_wgrad3(dY, I, ws, dW, db, N, IH, IW, IC, OH, OW, OC, stride, splits, pix_per_split, accumulate,
-                         taps, 1.f, st);
-}
-
 // Per-pixel dense weight gradient over a virtual channel concat [I | I2]
 // (I: [rows, C1], I2: [rows, IC - C1], C1 % 128 == 0): dW [OC][IC].  Returns
 // -1 (nothing launched) when the buffer kernel cannot take the shape; the
@@ -3560,7 +3035,7 @@ D3D_API int d3d_conv_wgrad_cat(const void* dY, const void* I, const void* I2, in
                                int rows, int IC, int OC, int splits, int pix_per_split, int accumulate,
                                hipStream_t st) {
   constexpr int BM = 128, BN = 128;
-  if (g_wgrad_impl < 5 || C1 % BN || (long)rows * IC * 2 >= (1L << 30) ||
+  if (g_wgrad_impl < WGRAD_BUFL || C1 % BN || (long)rows * IC * 2 >= (1L << 30) ||
       (long)pix_per_split * OC * 2 >= (1L << 31))
     return -1;
   const bool wide_long = (long)OC * IC >= (4L << 20) && pix_per_split > 16384;
@@ -3577,7 +3052,7 @@ D3D_API int d3d_conv_wgrad_cat(const void* dY, const void* I, const void* I2, in
 
 // Weight gradient of a GEMM whose output rows are split over nseg parameters
 // (row0[s] = first row of segment s, ascending; wdst[s] / bdst[s] = that
-// parameter's dW / db, bdst entries may be null).  ws as for d3d_conv_wgrad2
+// parameter's dW / db, bdst entries may be null).  ws as for d3d_conv_wgrad3
 // plus 2*splits*OC floats when any bdst is non-null.
 D3D_API int d3d_conv_wgrad_seg(const void* dY, const void* I, float* ws, int N, int IH, int IW, int IC, int OH,
                                int OW, int OC, int stride, int splits, int pix_per_split, int accumulate, int taps,
@@ -3632,19 +3107,6 @@ D3D_API int d3d_wgrad_scatter(const float* ws, int OC, int IC, int splits, int a
   return (int)hipGetLastError();
 }
 
-D3D_API int d3d_conv_wgrad(const void* dY, const void* I, float* ws, float* dW, int N, int IH, int IW, int IC, int OH,
-                           int OW, int OC, int stride, int splits, int pix_per_split, int accumulate, int taps,
-                           hipStream_t st) {
-  return d3d_conv_wgrad2(dY, I, ws, dW, nullptr, N, IH, IW, IC, OH, OW, OC, stride, splits, pix_per_split,
-                         accumulate, taps, st);
-}
-
-D3D_API int d3d_conv3x3_wgrad(const void* dY, const void* I, float* ws, float* dW, int N, int IH, int IW, int IC,
-                              int OH, int OW, int OC, int stride, int splits, int pix_per_split, int accumulate,
-                              hipStream_t st) {
-  return d3d_conv_wgrad(dY, I, ws, dW, N, IH, IW, IC, OH, OW, OC, stride, splits, pix_per_split, accumulate, 9, st);
-}
-
 // per-image (optional) and total channel sums of dY [N, P, C] (C % 8 == 0).
 // part: workspace [(nchunks + 1) * N * C + 64 * C] fp32.
 D3D_API int d3d_chansum(const void* dY, float* part, float* per_img, float* tot, int N, int P, int C, int nchunks,
@@ -3666,9 +3128,4 @@ D3D_API int d3d_pack_weight(const float* w, void* out, int OC, int IC, int OCp, 
   if (g > 4096) g = 4096;
   hipLaunchKernelGGL(pack_w_k, dim3((int)g), dim3(256), 0, st, w, (bf16*)out, OC, IC, OCp, ICp, trans, taps);
   return (int)hipGetLastError();
-}
-
-D3D_API int d3d_pack_conv_weight(const float* w, void* out, int OC, int IC, int OCp, int ICp, int trans,
-                                 hipStream_t st) {
-  return d3d_pack_weight(w, out, OC, IC, OCp, ICp, trans, 9, st);
 }

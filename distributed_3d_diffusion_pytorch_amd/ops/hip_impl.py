@@ -60,28 +60,33 @@ _FILM_EARLY = int(os.environ.get("D3D_FILM_EARLY_WGRAD", "0"))
 _FILM_INLINE = os.environ.get("D3D_FILM_WGRAD_INLINE", "0") == "1"
 
 
+# Kernel ceilings, by name: the values of conv.hip's ConvImpl / WgradImpl enums
+# (documented there).  A ceiling is the most specialised kernel the dispatcher
+# may pick; shapes that kernel does not take fall down the ladder.
+_CONV_IMPLS = {"bufl": 3, "w8": 4, "w8w": 6, "w8n": 7, "halo": 8}
+_WGRAD_IMPLS = {"reg": 0, "bufl": 5, "w8": 6}
+
+
 def set_conv_impl(impl: str) -> None:
-    """'bufl' (default: buffer-descriptor LDS-DMA pipelined MFMA kernel),
-    'glds' (flat-address LDS-DMA) or 'reg' (register-staged); the latter two
-    are kept for A/B measurements and for operands beyond 2 GiB."""
+    """Forward / input-gradient conv ceiling (for tests and A/B measurements):
+    'bufl'  conv_bufl_k, 128 x 128 tiles, split-K on small grids;
+    'w8'    + conv_w8_k 256 x 256 tiles where they fill the chip;
+    'w8w'   + its 128 x 512 tiles for 128 / 384-channel layers;
+    'w8n'   + its 256 x 128 tiles where 256 x 256 ones leave CUs idle;
+    'halo'  (default) 'w8w' + conv_halo_k on stride-1 3x3 convs.
+    At every ceiling small grids run the conv_small.hip kernels, and what
+    the buffer-descriptor kernels cannot take (transposed convs with stride
+    > 1, operands past 2 GiB) runs the flat-address conv_glds_k."""
     dev = torch.cuda.current_device()
     if dev not in _ZERO_PAGE:
         _ZERO_PAGE[dev] = torch.zeros(64, dtype=BF16, device="cuda")
-    _chk(_lib.d3d_set_conv_impl({"reg": 0, "glds": 1, "bufl": 2, "bufl1": 3, "w8": 4, "w8w": 6, "w8n": 7, "halo": 8}[impl], _ZERO_PAGE[dev].data_ptr()), "set_conv_impl")
-
-
-def set_conv_korder(korder: int) -> None:
-    """glds conv k-step order (1: channel-chunk major, default; 0: tap major)."""
-    _chk(_lib.d3d_set_conv_korder(int(korder)), "set_conv_korder")
-
-
-_WGRAD_IMPLS = {"reg": 0, "glds": 1, "glds64x2": 1, "glds32x2": 2, "glds32x3": 3, "glds64x3": 4, "bufl": 5,
-                "w8": 6}
+    _chk(_lib.d3d_set_conv_impl(_CONV_IMPLS[impl], _ZERO_PAGE[dev].data_ptr()), "set_conv_impl")
 
 
 def set_wgrad_impl(impl: str) -> None:
-    """Weight-gradient kernel: 'reg' (register-staged, padded LDS rows) or a
-    DMA-staged variant 'glds<pixels per stage>x<stages>'."""
+    """Weight-gradient ceiling: 'reg' (conv_wgrad_k, register-staged: the
+    catch-all), 'bufl' (+ conv_wgrad_bufl_k, buffer-descriptor LDS-DMA) or
+    'w8' (default: + the 8-wave conv_wgrad_w8_k)."""
     _chk(_lib.d3d_set_wgrad_impl(_WGRAD_IMPLS[impl]), "set_wgrad_impl")
 
 
@@ -90,7 +95,6 @@ _IMPL_SET = [False]
 
 def _ensure_impl():
     if not _IMPL_SET[0]:
-        import os
         set_conv_impl("halo")
         set_wgrad_impl("w8")
         _IMPL_SET[0] = True
@@ -825,7 +829,7 @@ def gn_film(x, weight, bias, ss, groups=32, eps=1e-5, dropout_p=0.0, training=Fa
 # ----------------------------------------------------------------- conv ----
 if os.environ.get("D3D_GEMM_TUNE"):     # A/B knob "cfg,gm,grid" (gemm.hip d3d_gemm_tune; 0 keeps a value)
     _lib.d3d_gemm_tune(*[int(v) for v in os.environ["D3D_GEMM_TUNE"].split(",")])
-if os.environ.get("D3D_HALO_AU"):        # A/B knob: halo conv with unrolled taps / precomputed offsets (1) or not (0)
+if os.environ.get("D3D_HALO_AU"):        # A/B knob: which halo conv tiles are on (conv.hip d3d_conv_halo_cfg bits)
     _lib.d3d_conv_halo_cfg(int(os.environ["D3D_HALO_AU"]))
 if os.environ.get("D3D_GEMM_SMALL_K"):   # A/B knob: 128x128 tiles for short-K 256-768-channel GEMMs (1) or not (0)
     _lib.d3d_gemm_small_k(int(os.environ["D3D_GEMM_SMALL_K"]))

@@ -419,6 +419,18 @@ def test_conv3x3_wgrad_w8(H, N, Hh, W, Ci, Co, s, res, rb, scale):
         H.set_wgrad_impl("w8")
 
 
+@pytest.mark.parametrize("N,Hh,W,Ci,Co,s,res,rb,scale", [CONV_SHAPES[2], CONV_SHAPES[5], CONV_SHAPES[8]])
+def test_conv3x3_wgrad_reg(H, N, Hh, W, Ci, Co, s, res, rb, scale):
+    """conv_wgrad_k, the weight gradient's catch-all (the default ladder reaches
+    it only at very large shapes): a 3x3 same-size case, a strided one with a
+    144-channel tail, a non-power-of-two image."""
+    H.set_wgrad_impl("reg")
+    try:
+        test_conv3x3(H, N, Hh, W, Ci, Co, s, res, rb, scale)
+    finally:
+        H.set_wgrad_impl("w8")
+
+
 @pytest.mark.parametrize("cfg", [8, 4, 2])
 @pytest.mark.parametrize("M,N,K,lda,ldb,ldo,bias,res,alpha,scale", [
     (256, 256, 128, 128, 128, 256, False, False, 1.0, 1.0),
@@ -2087,7 +2099,7 @@ def test_kernels_bitwise_under_coresidency():
 def test_conv_operands_beyond_2gib(H):
     """Large-operand path (128x128 images at one micro-batch of 128): a 3x3
     conv whose input exceeds the kernels' 32-bit buffer offsets runs as
-    image chunks at full speed (d3d_conv2), and the weight gradient over a
+    image chunks at full speed (d3d_conv3), and the weight gradient over a
     > 1 GiB input stays on the descriptor-rebased fast kernels; both against
     the fp32 torch composition."""
     torch.manual_seed(0)

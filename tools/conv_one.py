@@ -11,13 +11,13 @@ import torch
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--impl", default="w8")
+    ap.add_argument("--impl", default="w8", help="conv ceiling: bufl|w8|w8w|w8n|halo")
     ap.add_argument("--n", type=int, default=128)
     ap.add_argument("--h", type=int, default=64)
     ap.add_argument("--ci", type=int, default=128)
     ap.add_argument("--co", type=int, default=128)
     ap.add_argument("--dgrad", action="store_true")
-    ap.add_argument("--wgrad", default="", help="weight-gradient kernel impl (reg|bufl|...) instead of fwd")
+    ap.add_argument("--wgrad", default="", help="weight-gradient ceiling (reg|bufl|w8) instead of fwd")
     ap.add_argument("--iters", type=int, default=20)
     a = ap.parse_args()
     from distributed_3d_diffusion_pytorch_amd.ops import hip_impl as H

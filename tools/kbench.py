@@ -49,7 +49,6 @@ def main():
     ap.add_argument("--batch", type=int, default=64, help="examples (frame batch N = 2*batch)")
     ap.add_argument("--iters", type=int, default=20)
     ap.add_argument("--torch", action="store_true", help="also time the torch composition")
-    ap.add_argument("--only_glds_check", action="store_true")
     a = ap.parse_args()
     dev = "cuda"
     N = 2 * a.batch
@@ -82,7 +81,7 @@ def main():
                 rep("conv_fwd", shp, "hip-" + impl,
                     timeit(lambda: H._conv_fwd(x, wp, b, None, None, y, N, Hh, Hh, Ci, H._up(Ci, 64), OH, OH, Co, Co,
                                                s, False, 1.0), a.iters), fl)
-            H.set_conv_impl("bufl")
+            H.set_conv_impl("halo")
             if a.torch:
                 wb, bb = w.to(BF), b.to(BF)
                 xc = x.permute(0, 3, 1, 2)
@@ -96,13 +95,13 @@ def main():
                 rep("conv_dgrad", shp, "hip-" + impl,
                     timeit(lambda: H._conv_fwd(g, wt, None, None, None, dx, N, OH, OH, Co, H._up(Co, 64), Hh, Hh, Ci,
                                                Ci, s, True, 1.0), a.iters), fl)
-            H.set_conv_impl("bufl")
+            H.set_conv_impl("halo")
         if "wgrad" in ops:
             for impl in ("bufl", "w8"):
                 H.set_wgrad_impl(impl)
                 rep("conv_wgrad", shp, "hip-" + impl,
                     timeit(lambda: H._wgrad(g, x, Co, Ci, N, Hh, Hh, OH, OH, s, 9), a.iters), fl)
-            H.set_wgrad_impl("bufl")
+            H.set_wgrad_impl("w8")
     if "linear" in ops:
         for (P, Ci, Co) in [(N * 4096, 1024, 2048), (N * 1024, 1024, 4608), (N * 256, 1024, 4608),
                             (N * 64, 1024, 3072), (N * 256, 256, 768), (N * 64, 512, 1536), (N * 4096, 384, 128),
@@ -116,12 +115,12 @@ def main():
             wp = H.packed_weight(w, False, 1)
             y = torch.empty(P, 1, 1, Co, dtype=BF, device=dev)
             g = torch.randn(P, 1, 1, Co, device=dev).to(BF)
-            for impl in ("bufl1", "w8w"):
+            for impl in ("bufl", "w8w"):
                 H.set_conv_impl(impl)
                 rep("lin_fwd", shp, "hip-" + impl,
                     timeit(lambda: H._conv_fwd(x4, wp, b, None, None, y, P, 1, 1, Ci, H._up(Ci, 64), 1, 1, Co, Co, 1,
                                                False, 1.0, 0, 1), a.iters), fl)
-            H.set_conv_impl("w8w")
+            H.set_conv_impl("halo")
             wt = H.packed_weight(w, True, 1)
             g4 = torch.randn(P, 1, 1, Co, device=dev).to(BF)
             dx = torch.empty(P, 1, 1, Ci, dtype=BF, device=dev)
@@ -137,7 +136,7 @@ def main():
                 H.set_wgrad_impl(impl)
                 rep("lin_wgrad", shp, "hip-" + impl, timeit(lambda: H._wgrad(g, x4, Co, Ci, P, 1, 1, 1, 1, 1, 1),
                                                              a.iters), fl)
-            H.set_wgrad_impl("bufl")
+            H.set_wgrad_impl("w8")
             if a.torch:
                 wb = w.to(BF)
                 rep("lin_fwd", shp, "hipblaslt", timeit(lambda: torch.addmm(b.to(BF), x, wb.t()), a.iters), fl)

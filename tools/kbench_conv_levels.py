@@ -49,7 +49,6 @@ def timeit(fn, iters=25, reps=10):
 def main():
     ns = [int(a) for a in sys.argv[1:]] or [32, 256]
     H._ensure_impl()
-    H._lib.d3d_conv_res_cfg(int(os.environ.get("D3D_CONV_RES_ALWAYS", "0")))
     for N in ns:
         levels = [(64, 128, 128), (32, 256, 256), (16, 256, 256), (8, 512, 512)]
         if os.environ.get("KB_CONV_EXTRA"):             # level-entry convs (channel change) and decoder concat widths
@@ -74,7 +73,7 @@ def main():
             dx = torch.empty(N, Hh, Hh, C, device="cuda", dtype=BF)
             d = timeit(lambda: H._conv_fwd(g, wpt, None, None, None, dx, N, Hh, Hh, OC, OCp, Hh, Hh, C, C, 1, True,
                                            1.0))
-            print(json.dumps({"res_always": os.environ.get("D3D_CONV_RES_ALWAYS", "0"), "N": N, "level": f"{Hh}x{Hh}x{C}->{OC}", "fwd_us": round(f1, 1),
+            print(json.dumps({"N": N, "level": f"{Hh}x{Hh}x{C}->{OC}", "fwd_us": round(f1, 1),
                               "fwd_tfs": round(fl / f1 / 1e6, 1), "fwd_res_us": round(f2, 1),
                               "fwd_res_tfs": round(fl / f2 / 1e6, 1), "dgrad_us": round(d, 1),
                               "dgrad_tfs": round(fl / d / 1e6, 1)}), flush=True)
