@@ -1,5 +1,5 @@
 """Continuous-time DDPM math (cosine logSNR schedule, forward noising,
-ancestral CFG posterior).
+ancestral CFG posterior, the few-step DDIM / DPM-Solver++(2M) updates).
 
 Parity targets (all device-agnostic here; the reference runs parts of this on
 the CPU, D11):
@@ -14,7 +14,7 @@ posterior and noise in one launch per step).
 from __future__ import annotations
 
 import math
-from typing import Tuple
+from typing import List, Optional, Sequence, Tuple
 
 import torch
 
@@ -56,11 +56,22 @@ def diffusion_loss(eps: torch.Tensor, eps_hat: torch.Tensor, loss_type: str = "l
     raise NotImplementedError(loss_type)
 
 
+SPACINGS = ("t", "logsnr")
+SOLVERS = ("ancestral", "ddim", "dpmpp2m")
+
+
 def sampler_logsnrs(timesteps: int, logsnr_min: float = -20.0, logsnr_max: float = 20.0,
-                    dtype=torch.float32) -> Tuple[torch.Tensor, torch.Tensor]:
-    """(lambda_k, lambda_{k+1}) for t_k = 1 - k/T, k=0..T-1 (`sampling.py:134-135`)."""
-    ts = torch.linspace(1.0, 0.0, timesteps + 1, dtype=dtype)
-    lam = logsnr_schedule_cosine(ts, logsnr_min=logsnr_min, logsnr_max=logsnr_max)
+                    dtype=torch.float32, spacing: str = "t") -> Tuple[torch.Tensor, torch.Tensor]:
+    """(lambda_k, lambda_{k+1}), k=0..T-1.  ``spacing="t"``: t_k = 1 - k/T on
+    the cosine schedule (`sampling.py:134-135`); ``"logsnr"``: lambda uniform
+    from logsnr_min to logsnr_max (equal solver step sizes h)."""
+    if spacing == "t":
+        ts = torch.linspace(1.0, 0.0, timesteps + 1, dtype=dtype)
+        lam = logsnr_schedule_cosine(ts, logsnr_min=logsnr_min, logsnr_max=logsnr_max)
+    elif spacing == "logsnr":
+        lam = torch.linspace(logsnr_min, logsnr_max, timesteps + 1, dtype=dtype)
+    else:
+        raise ValueError(f"spacing {spacing!r}: expected one of {SPACINGS}")
     return lam[:-1], lam[1:]
 
 
@@ -81,3 +92,80 @@ def cfg_posterior(z: torch.Tensor, eps_cond: torch.Tensor, eps_uncond: torch.Ten
     mean = alpha_next * (z * (1.0 - c) / alpha + c * x0)
     var = torch.sigmoid(-logsnr_next) * c
     return mean, var
+
+
+# ------------------------------------------------------- few-step solvers
+# One step lambda -> lambda' of every solver is the linear update
+#     z' = kz z + k0 x0 + k1 x0_prev + kn N(0,1),
+# x0 = clamp((z - sigma eps)/alpha, -1, 1) the guided data prediction and
+# x0_prev the previous step's.  With h = (lambda' - lambda)/2 and
+# c = -expm1(lambda - lambda'):
+#   ddim (eta in [0,1]):  s = eta sigma' sqrt(c) (0 on the last step),
+#       g = sqrt(sigma'^2 - s^2)/sigma;  kz = g, k0 = alpha' - g alpha, kn = s
+#       (eta = 1 is the ancestral posterior, eta = 0 the probability-flow step)
+#   dpmpp2m (DPM-Solver++ 2M, data prediction):  q = -alpha' expm1(-h),
+#       kz = sigma'/sigma;  first and LAST step first order (k0 = q), else with
+#       r = h_prev/h:  k0 = q (1 + 1/(2r)), k1 = -q/(2r)
+# The last step of the cosine schedule is a big logSNR jump: extrapolating x0
+# over it costs more than the second order gains, hence the first-order final
+# step (the "lower_order_final" rule of the DPM-Solver authors).
+def _sig(x: float) -> float:
+    return 1.0 / (1.0 + math.exp(-x)) if x >= 0 else math.exp(x) / (1.0 + math.exp(x))
+
+
+def solver_row(lam: Sequence[float], lam_next: Sequence[float], k: int, solver: str = "ddim", eta: float = 0.0,
+               lam0: float = 20.0, first_order: bool = False) -> List[float]:
+    """The 8 per-step scalars ``[lambda, alpha, sigma, kz, k0, k1, kn,
+    lambda0]`` of step ``k`` of the schedule ``(lam, lam_next)`` (lists of
+    ``sampler_logsnrs``), computed in fp64; slots 0 and 7 are what the CFG
+    input assembly reads.  ``first_order``: the dpmpp2m step without history
+    (what a step takes when no previous x0 is at hand)."""
+    if solver not in ("ddim", "dpmpp2m"):
+        raise ValueError(f"solver {solver!r}: expected 'ddim' or 'dpmpp2m'")
+    if not 0.0 <= eta <= 1.0:
+        raise ValueError(f"eta {eta}: expected a value in [0, 1]")
+    if solver == "dpmpp2m" and eta != 0.0:
+        raise ValueError("dpmpp2m is deterministic: eta must be 0")
+    T = len(lam)
+    l, ln = float(lam[k]), float(lam_next[k])
+    alpha, sigma = math.sqrt(_sig(l)), math.sqrt(_sig(-l))
+    alpha_n, sigma_n = math.sqrt(_sig(ln)), math.sqrt(_sig(-ln))
+    h = 0.5 * (ln - l)
+    k1 = kn = 0.0
+    if solver == "ddim":
+        e = eta if k < T - 1 else 0.0
+        c = -math.expm1(l - ln)
+        # sigma'^2 - s^2 = sigma'^2 m with m = 1 - eta^2 c = (1 - eta^2) + eta^2 exp(lambda - lambda'):
+        # no cancellation; alpha' - g alpha = -alpha' expm1(-h + log(m)/2) likewise
+        m = (1.0 - e * e) + e * e * math.exp(l - ln)
+        kn = e * sigma_n * math.sqrt(c)
+        kz = sigma_n * math.sqrt(m) / sigma
+        k0 = -alpha_n * math.expm1(-h + 0.5 * math.log(m)) if m > 0.0 else alpha_n
+    else:
+        q = -alpha_n * math.expm1(-h)
+        kz = sigma_n / sigma
+        k0 = q
+        if not first_order and 0 < k < T - 1:
+            r = 0.5 * (l - float(lam[k - 1])) / h
+            k0, k1 = q * (1.0 + 0.5 / r), -0.5 * q / r
+    return [l, alpha, sigma, kz, k0, k1, kn, float(lam0)]
+
+
+def solver_step(z: torch.Tensor, eps_cond: torch.Tensor, eps_uncond: torch.Tensor, w: torch.Tensor,
+                x0_prev: Optional[torch.Tensor], row, noise: Optional[torch.Tensor]
+                ) -> Tuple[torch.Tensor, torch.Tensor]:
+    """One solver step in the dtype of ``z``: ``(z', x0)`` from a
+    ``solver_row`` (8 floats or a tensor of them).  ``x0_prev`` is read only
+    when the row's k1 != 0, ``noise`` only when kn != 0 (either may be None
+    otherwise); the returned clamped x0 is the next step's ``x0_prev``."""
+    _, alpha, sigma, kz, k0, k1, kn = (float(v) for v in row[:7])
+    shape = (-1,) + (1,) * (z.dim() - 1)
+    w = w.to(z.dtype).view(shape)
+    eps = (1.0 + w) * eps_cond - w * eps_uncond
+    x0 = ((z - sigma * eps) / alpha).clamp(-1.0, 1.0)
+    out = kz * z + k0 * x0
+    if k1 != 0.0:
+        out = out + k1 * x0_prev.to(z.dtype)
+    if kn != 0.0:
+        out = out + kn * noise.to(z.dtype)
+    return out, x0

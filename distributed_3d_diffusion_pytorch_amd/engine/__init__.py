@@ -1,7 +1,7 @@
 from .optim import FusedAdam, ema_decay_for, warmup_lr
 from .trainer import Trainer
-from .sampler import DiffusionSampler, RecordEntry, shard_range
+from .sampler import DiffusionSampler, RecordEntry, SolverState, shard_range
 from .evaluate import EvalObject, evaluate_objects, heldout_loss, load_objects, summarize
 
-__all__ = ["FusedAdam", "ema_decay_for", "warmup_lr", "Trainer", "DiffusionSampler", "RecordEntry",
+__all__ = ["FusedAdam", "ema_decay_for", "warmup_lr", "Trainer", "DiffusionSampler", "RecordEntry", "SolverState",
            "shard_range", "EvalObject", "evaluate_objects", "heldout_loss", "load_objects", "summarize"]

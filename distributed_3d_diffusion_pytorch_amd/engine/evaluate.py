@@ -103,7 +103,8 @@ def evaluate_objects(model, objects: Sequence[EvalObject], input_view: int = 0, 
                      w: Sequence[float] = (3.0,), timesteps: int = 256, batch: int = 64,
                      autoregressive: bool = False, seed: int = 0, device=None, ref_quirk: bool = False,
                      graph: Optional[bool] = None, keep_images: bool = False,
-                     on_view: Optional[Callable] = None):
+                     on_view: Optional[Callable] = None, solver: str = "ancestral", eta: float = 0.0,
+                     spacing: str = "t"):
     """Generate ``views`` of every object from its ``input_view`` and score
     them.  Returns ``(rows, images)``: one row ``{instance, view, w, chain,
     mse, psnr, ssim}`` per (object, view, w) -- ``chain`` the global chain
@@ -111,7 +112,8 @@ def evaluate_objects(model, objects: Sequence[EvalObject], input_view: int = 0, 
     with ``keep_images``, ``images[(instance, view)]`` = the generated
     [len(w),3,H,W] batch on the CPU.  ``on_view(objects, view, out, gt)`` is
     called with each generated batch ([G * len(w),3,H,W], object-major) and
-    its ground truth [G,3,H,W]."""
+    its ground truth [G,3,H,W].  ``solver`` / ``eta`` / ``spacing``: the
+    update rule and step spacing of :class:`DiffusionSampler`."""
     dev = torch.device(device) if device is not None else next(model.parameters()).device
     nw = len(w)
     rows: List[dict] = []
@@ -120,7 +122,8 @@ def evaluate_objects(model, objects: Sequence[EvalObject], input_view: int = 0, 
         objs = objects[s:s + max(int(batch), 1)]
         G = len(objs)
         # chains are object-major and numbered globally, so a row (and its noise) does not depend on `batch`
-        smp = DiffusionSampler(model, timesteps, ref_quirk, seed=seed, device=dev, chain_offset=s * nw, graph=graph)
+        smp = DiffusionSampler(model, timesteps, ref_quirk, seed=seed, device=dev, chain_offset=s * nw, graph=graph,
+                               solver=solver, eta=eta, spacing=spacing)
         group = torch.arange(G).repeat_interleave(nw)
         wv = torch.tensor([float(x) for x in w]).repeat(G)
         K = torch.stack([o.K for o in objs]).to(dev)

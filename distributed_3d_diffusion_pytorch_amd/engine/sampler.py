@@ -30,7 +30,13 @@ Differences by design (same math, §2.5 of SURVEY):
   single step: the conditioning is computed for the 2G classes (cond / uncond
   per group) and read through the same row -> class map;
 * D9 (noise skipped at t=0.5 where logsnr_next == 0) is opt-in via
-  ``ref_quirk``; default adds noise on every step but the last.
+  ``ref_quirk``; default adds noise on every step but the last;
+* few-step solvers next to the ancestral chain: ``solver="ddim"`` (eta in
+  [0, 1]) and ``solver="dpmpp2m"`` (DPM-Solver++ 2M), steps uniform in t or in
+  logSNR.  Every solver step is one linear update of (z, x0, previous x0,
+  noise) with host-computed fp64 coefficients (``diffusion.solver_row``), so
+  the graphed step is the same three stages with `sampler_solve_k` last and a
+  static history buffer; the ancestral path is untouched.
 """
 from __future__ import annotations
 
@@ -40,7 +46,8 @@ from typing import List, Optional, Tuple
 
 import torch
 
-from ..diffusion import logsnr_schedule_cosine, sampler_logsnrs, cfg_posterior
+from ..diffusion import (logsnr_schedule_cosine, sampler_logsnrs, cfg_posterior, solver_row, solver_step, SOLVERS,
+                         SPACINGS)
 
 _M64 = (1 << 64) - 1
 _GOLDEN = 0x9E3779B97F4A7C15
@@ -53,15 +60,47 @@ class RecordEntry:
         self.img, self.R, self.T = img, R, T
 
 
+class SolverState:
+    """History of a multistep solver across :meth:`DiffusionSampler.step`
+    calls: ``x0_prev`` [b,3,H,W], the previous step's clamped data prediction
+    (None before the first step)."""
+
+    def __init__(self):
+        self.x0_prev: Optional[torch.Tensor] = None
+
+
 class DiffusionSampler:
     def __init__(self, model: torch.nn.Module, timesteps: int = 256, ref_quirk: bool = False,
                  logsnr_min: float = -20.0, logsnr_max: float = 20.0, seed: int = 0, device=None,
-                 chain_offset: int = 0, graph: Optional[bool] = None, share_cond: bool = True):
+                 chain_offset: int = 0, graph: Optional[bool] = None, share_cond: bool = True, *,
+                 solver: str = "ancestral", eta: float = 0.0, spacing: str = "t"):
         """``chain_offset``: global index of this sampler's first chain (its
         rank's shard start).  ``graph``: replay the step from a HIP graph
         (default: on for the bf16 HIP path).  ``share_cond``: compute the
         conditioning once per class instead of once per chain in
-        :meth:`sample` (identical result)."""
+        :meth:`sample` (identical result).
+
+        ``solver``: ``"ancestral"`` (the reference's chain), ``"ddim"`` (with
+        ``eta`` in [0, 1]: 0 deterministic, 1 the ancestral variance) or
+        ``"dpmpp2m"`` (DPM-Solver++ 2M, deterministic) -- the update rules of
+        ``diffusion.solver_row``; ``spacing``: the steps uniform in ``"t"`` on
+        the cosine schedule or uniform in ``"logsnr"``.
+
+        A multistep solver keeps the previous step's data prediction.  With
+        stochastic conditioning and more than one record entry that prediction
+        was made under another conditioning view than the current step's; it is
+        used as it is (the chain stays deterministic in the seed)."""
+        if solver not in SOLVERS:
+            raise ValueError(f"solver {solver!r}: expected one of {SOLVERS}")
+        if spacing not in SPACINGS:
+            raise ValueError(f"spacing {spacing!r}: expected one of {SPACINGS}")
+        if not 0.0 <= float(eta) <= 1.0:
+            raise ValueError(f"eta {eta}: expected a value in [0, 1]")
+        if solver == "dpmpp2m" and float(eta) != 0.0:
+            raise ValueError("dpmpp2m is deterministic: eta must be 0")
+        if ref_quirk and solver != "ancestral":
+            raise ValueError("ref_quirk is a property of the ancestral chain: solver must be 'ancestral'")
+        self.solver, self.eta, self.spacing = solver, float(eta), spacing
         self.share_cond = bool(share_cond)
         self.model = model
         self.T = timesteps
@@ -71,7 +110,7 @@ class DiffusionSampler:
         self.seed_base = (int(seed) * 0x2545F4914F6CDD1D + 0x5DEECE66D) & _M64
         self.c0 = int(chain_offset)
         self.choice_rng = random.Random(seed)
-        lam, lam_next = sampler_logsnrs(timesteps, logsnr_min, logsnr_max)
+        lam, lam_next = sampler_logsnrs(timesteps, logsnr_min, logsnr_max, spacing=spacing)
         self.lam, self.lam_next = lam.tolist(), lam_next.tolist()
         self.lam0 = float(logsnr_schedule_cosine(torch.zeros(()), logsnr_min=logsnr_min, logsnr_max=logsnr_max))
         self.graph = graph
@@ -93,6 +132,17 @@ class DiffusionSampler:
         c = -math.expm1(lam - lam_next)
         return [lam, math.sqrt(sig(lam)), math.sqrt(sig(-lam)), math.sqrt(sig(lam_next)), c,
                 math.sqrt(sig(-lam_next) * c), 1.0 if self.add_noise(k) else 0.0, self.lam0]
+
+    def solver_params(self, k: int, first_order: bool = False) -> List[float]:
+        """[lambda, alpha, sigma, kz, k0, k1, kn, lambda0] of a ddim / dpmpp2m
+        step (the device block of sampler_inputs_k / sampler_solve_k);
+        ``first_order``: the step without history."""
+        return solver_row(self.lam, self.lam_next, k, self.solver, self.eta, self.lam0, first_order)
+
+    def _table(self) -> torch.Tensor:
+        """The per-step device rows of the graphed step, [T, 8] fp32."""
+        rows = [self.params(k) if self.solver == "ancestral" else self.solver_params(k) for k in range(self.T)]
+        return torch.tensor(rows, dtype=torch.float32).to(self.device)
 
     def _hip(self, z: torch.Tensor) -> bool:
         from .. import ops
@@ -171,18 +221,31 @@ class DiffusionSampler:
         return eps[:b], eps[b:]
 
     @torch.no_grad()
-    def step(self, z, x_cond, R, T, K, w, k: int, shared: bool = False, group=None):
-        """One ancestral CFG step for b chains.  ``shared``: every chain has
-        the same R/T/K (conditioning computed once per class).  ``group``
-        (int [b], values in [0, G)): R [G,2,3,3], T [G,2,3] and K [G,3,3] are
-        per group and chain j is conditioned on group[j]'s (conditioning
-        computed once per group and class)."""
+    def step(self, z, x_cond, R, T, K, w, k: int, shared: bool = False, group=None,
+             state: Optional[SolverState] = None):
+        """One CFG step of the sampler's solver for b chains.  ``shared``:
+        every chain has the same R/T/K (conditioning computed once per class).
+        ``group`` (int [b], values in [0, G)): R [G,2,3,3], T [G,2,3] and K
+        [G,3,3] are per group and chain j is conditioned on group[j]'s
+        (conditioning computed once per group and class).  ``state``: the
+        :class:`SolverState` a multistep solver reads the previous data
+        prediction from and stores this step's in; without one (or before its
+        first step) the step is first order.  The ancestral solver ignores it."""
         from ..ops import torch_impl as TI
         if group is not None:
             self._check_group(group, z.shape[0], R.shape[0])
         if self._hip(z):
-            return self._hip_step(z, x_cond, R, T, K, w, k, shared, group)
+            return self._hip_step(z, x_cond, R, T, K, w, k, shared, group, state)
         eps_c, eps_u = self.denoise_eps(x_cond, z, R, T, K, self.lam[k], k, shared, group)
+        if self.solver != "ancestral":
+            x0_prev = state.x0_prev if state is not None else None
+            row = self.solver_params(k, first_order=x0_prev is None)
+            noise = self._noise(TI.K_NZ, k, tuple(z.shape), z.device) if row[6] != 0.0 else None
+            # (the fp32 row the device table holds, so the CPU and the HIP path take the same step)
+            z, x0 = solver_step(z, eps_c, eps_u, w, x0_prev, torch.tensor(row, dtype=torch.float32), noise)
+            if state is not None:
+                state.x0_prev = x0
+            return z
         mean, var = cfg_posterior(z, eps_c, eps_u, w, torch.tensor(self.lam[k]), torch.tensor(self.lam_next[k]))
         if not self.add_noise(k):
             return mean
@@ -198,12 +261,20 @@ class DiffusionSampler:
         return grp
 
     @torch.no_grad()
-    def _hip_step(self, z, x_cond, R, T, K, w, k, shared=False, group=None):
+    def _hip_step(self, z, x_cond, R, T, K, w, k, shared=False, group=None, state=None):
         """Eager form of the graphed step (same kernels, host seed)."""
         from ..ops import hip_impl
         b, _, H, W = z.shape
         dev = z.device
-        prm = torch.tensor(self.params(k), dtype=torch.float32).to(dev)
+        ancestral = self.solver == "ancestral"
+        if ancestral:
+            row = self.params(k)
+        else:
+            x0_prev = state.x0_prev if state is not None else None
+            row = self.solver_params(k, first_order=x0_prev is None)
+            if x0_prev is None:             # (k1 = 0: the kernel only writes it)
+                x0_prev = torch.empty(b, 3, H, W, dtype=torch.float32, device=dev)
+        prm = torch.tensor(row, dtype=torch.float32).to(dev)
         xz = torch.empty(4 * b, H, W, 8, dtype=torch.bfloat16, device=dev)
         logsnr = torch.empty(2 * b, 2, dtype=torch.float32, device=dev)
         z = z.float().contiguous().clone()
@@ -220,7 +291,12 @@ class DiffusionSampler:
             batch = {"xz": xz, "logsnr": logsnr, "R": torch.cat([R, R]), "t": torch.cat([T, T]),
                      "K": torch.cat([K, K])}
             y = self.model(batch, cond_mask=mask, head_nhwc=True)
-        hip_impl.sampler_step2(z, y, w.float().contiguous(), prm, None, self.step_seed(k), self.c0)
+        if ancestral:
+            hip_impl.sampler_step2(z, y, w.float().contiguous(), prm, None, self.step_seed(k), self.c0)
+            return z
+        hip_impl.sampler_solve(z, x0_prev, y, w.float().contiguous(), prm, None, self.step_seed(k), self.c0)
+        if state is not None:
+            state.x0_prev = x0_prev
         return z
 
     # ------------------------------------------------------ graph step
@@ -238,7 +314,9 @@ class DiffusionSampler:
         g["t"][:, 1] = target_T.to(dev).float()
         g["K"] = K.to(dev).float().reshape(1, 3, 3).expand(nb, 3, 3).contiguous()
         g["w"] = w.to(dev).float().contiguous()
-        g["prm_table"] = torch.tensor([self.params(k) for k in range(self.T)], dtype=torch.float32).to(dev)
+        g["prm_table"] = self._table()
+        if self.solver != "ancestral":
+            g["x0"] = torch.zeros(b, 3, H, W, device=dev)        # the solver's history: previous data prediction
         g["prm"] = g["prm_table"][0].clone()
         g["sd"] = torch.zeros(3, dtype=torch.int64, device=dev)
         g["xz"] = torch.empty(4 * b, H, W, 8, dtype=torch.bfloat16, device=dev)
@@ -258,10 +336,20 @@ class DiffusionSampler:
             else:
                 batch = {"xz": g["xz"], "logsnr": g["logsnr"], "R": g["R"], "t": g["t"], "K": g["K"]}
                 y = self.model(batch, cond_mask=g["mask"], head_nhwc=True)
-            hip_impl.sampler_step2(g["z"], y, g["w"], g["prm"], g["sd"], self.seed_base, self.c0)
+            self._graph_update(g, y)
 
         self._g = self._capture(g, body)
         return g
+
+    def _graph_update(self, g: dict, y: torch.Tensor) -> None:
+        """The last launch of the graphed step: z (and the solver's history
+        ``g["x0"]``) updated in place from the head output.  Step 0 of every
+        solver has k1 = 0, so the history restarts with each run."""
+        from ..ops import hip_impl
+        if self.solver == "ancestral":
+            hip_impl.sampler_step2(g["z"], y, g["w"], g["prm"], g["sd"], self.seed_base, self.c0)
+        else:
+            hip_impl.sampler_solve(g["z"], g["x0"], y, g["w"], g["prm"], g["sd"], self.seed_base, self.c0)
 
     def _capture(self, g: dict, body) -> dict:
         """Warm ``body`` up on a side stream, capture it into ``g["graph"]``
@@ -299,7 +387,9 @@ class DiffusionSampler:
         g["z"] = torch.zeros(b, 3, H, W, device=dev)
         g["R"] = torch.zeros(2, G, 2, 3, 3, device=dev)
         g["t"] = torch.zeros(2, G, 2, 3, device=dev)
-        g["prm_table"] = torch.tensor([self.params(k) for k in range(self.T)], dtype=torch.float32).to(dev)
+        g["prm_table"] = self._table()
+        if self.solver != "ancestral":
+            g["x0"] = torch.zeros(b, 3, H, W, device=dev)        # the solver's history: previous data prediction
         g["prm"] = g["prm_table"][0].clone()
         g["sd"] = torch.zeros(3, dtype=torch.int64, device=dev)
         g["xz"] = torch.empty(4 * b, H, W, 8, dtype=torch.bfloat16, device=dev)
@@ -314,7 +404,7 @@ class DiffusionSampler:
             hip_impl.sampler_inputs(g["xc"], g["z"], g["prm"], g["sd"], self.seed_base, self.c0, g["xz"],
                                     g["logsnr"])
             y = self.model({"xz": g["xz"]}, shared_cond=g["sc"], head_nhwc=True)
-            hip_impl.sampler_step2(g["z"], y, g["w"], g["prm"], g["sd"], self.seed_base, self.c0)
+            self._graph_update(g, y)
 
         self._gg = self._capture(g, body)
         return g
@@ -382,11 +472,12 @@ class DiffusionSampler:
                 g["graph"].replay()
             z = g["z"].clone()
         else:
+            state = SolverState()           # (the history restarts with every run)
             for k in it:
                 e = record[self.choice_rng.randrange(len(record))]
                 R = torch.stack([e.R.to(dev), target_R.to(dev)], 0)[None].expand(b, 2, 3, 3).contiguous()
                 T = torch.stack([e.T.to(dev), target_T.to(dev)], 0)[None].expand(b, 2, 3).contiguous()
-                z = self.step(z, e.img.to(dev), R, T, Kb, w, k, shared=self.share_cond)
+                z = self.step(z, e.img.to(dev), R, T, Kb, w, k, shared=self.share_cond, state=state)
         if model_was_training:
             self.model.train()
         return z
@@ -465,12 +556,14 @@ class DiffusionSampler:
                 g["graph"].replay()
             z = g["z"].clone()
         else:
+            state = SolverState()
             for k in it:
                 i = self.choice_rng.randrange(L)
                 if self.share_cond:
-                    z = self.step(z, xcs[i], Rs[i], Ts[i], Kg, w, k, group=group_t)
+                    z = self.step(z, xcs[i], Rs[i], Ts[i], Kg, w, k, group=group_t, state=state)
                 else:
-                    z = self.step(z, xcs[i], Rs[i][group_t.long()], Ts[i][group_t.long()], Kg[group_t.long()], w, k)
+                    z = self.step(z, xcs[i], Rs[i][group_t.long()], Ts[i][group_t.long()], Kg[group_t.long()], w, k,
+                                  state=state)
         if model_was_training:
             self.model.train()
         return z

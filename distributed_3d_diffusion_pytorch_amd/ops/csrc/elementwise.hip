@@ -264,6 +264,45 @@ __global__ void sampler_step2_k(float* __restrict__ z, const bf16* __restrict__ 
   }
 }
 
+// Few-step solvers (DDIM, DPM-Solver++(2M); diffusion/schedule.py solver_row):
+// every solver is one linear update with host-computed coefficients,
+//   prm = [lambda, alpha, sigma, kz, k0, k1, kn, lambda0]
+//   eps = (1+w) ec - w eu;  x0 = clamp((z - sigma eps)/alpha, -1, 1)
+//   z' = kz z + k0 x0 + k1 x0_prev + kn N(0,1);  x0_prev' = x0
+// One thread per (chain, pixel): the conditional and the unconditional head
+// row y [2b,H,W,8] bf16 are one 16-byte load each, the three channel planes of
+// z / x0_prev [b,3,H,W] fp32 (both in place) are coalesced along the pixel.
+// x0_prev is read only when k1 != 0 (a fresh history buffer may hold anything)
+// and the noise -- same key and index as sampler_step2_k -- is drawn only when
+// kn != 0; both branches are uniform.
+__global__ void sampler_solve_k(float* __restrict__ z, float* __restrict__ x0p, const bf16* __restrict__ y,
+                                const float* __restrict__ w, int b, int HW, const float* __restrict__ prm,
+                                const uint64_t* __restrict__ sd, uint64_t seed, long c0) {
+  const uint64_t s = seed + (sd ? sd[0] : 0ull) * 0x9E3779B97F4A7C15ull;
+  const float alpha = prm[1], sigma = prm[2], kz = prm[3], k0 = prm[4], k1 = prm[5], kn = prm[6];
+  const bool hist = k1 != 0.f, noise = kn != 0.f;
+  GRID_LOOP(i, (long)b * HW) {
+    const int j = (int)(i / HW);
+    const int p = (int)(i - (long)j * HW);
+    const f32x8 ec = ld8(y + ((size_t)j * HW + p) * 8);
+    const f32x8 eu = ld8(y + ((size_t)(j + b) * HW + p) * 8);
+    const float wb = w[j];
+#pragma unroll
+    for (int ch = 0; ch < 3; ++ch) {
+      const size_t r = (size_t)ch * HW + p;
+      const size_t e = (size_t)j * 3 * HW + r;
+      const float eps = (1.f + wb) * ec[ch] - wb * eu[ch];
+      const float zi = z[e];
+      const float x0 = fminf(fmaxf((zi - sigma * eps) / alpha, -1.f), 1.f);
+      float m = kz * zi + k0 * x0;
+      if (hist) m += k1 * x0p[e];
+      if (noise) m += kn * normal01(s ^ K_NZ, (uint64_t)(c0 + j) * 3 * HW + r);
+      z[e] = m;
+      x0p[e] = x0;
+    }
+  }
+}
+
 // Counter-based N(0,1) fill: out[i] = N(seed ^ key, off + i)
 __global__ void randn_hash_k(float* __restrict__ out, long n, uint64_t seed, long off) {
   GRID_LOOP(i, n) out[i] = normal01(seed, (uint64_t)(off + i));
@@ -485,6 +524,13 @@ D3D_API int d3d_sampler_step2(float* z, const void* y, const float* w, int b, in
                               const void* sd, unsigned long long seed, long c0, hipStream_t st) {
   long total = (long)b * 3 * HW;
   hipLaunchKernelGGL(sampler_step2_k, dim3(ew_grid(total)), dim3(256), 0, st, z, (const bf16*)y, w, b, HW, prm,
+                     (const uint64_t*)sd, (uint64_t)seed, c0);
+  return (int)hipGetLastError();
+}
+D3D_API int d3d_sampler_solve(float* z, float* x0p, const void* y, const float* w, int b, int HW, const float* prm,
+                              const void* sd, unsigned long long seed, long c0, hipStream_t st) {
+  long total = (long)b * HW;
+  hipLaunchKernelGGL(sampler_solve_k, dim3(ew_grid(total)), dim3(256), 0, st, z, x0p, (const bf16*)y, w, b, HW, prm,
                      (const uint64_t*)sd, (uint64_t)seed, c0);
   return (int)hipGetLastError();
 }

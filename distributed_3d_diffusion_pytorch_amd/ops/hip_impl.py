@@ -2775,6 +2775,19 @@ def sampler_step2(z, y, w, prm, sd, seed, c0):
                                 int(seed) & 0xFFFFFFFFFFFFFFFF, int(c0), _st()), "sampler_step2")
 
 
+def sampler_solve(z, x0_prev, y, w, prm, sd, seed, c0):
+    """Few-step solver update (``diffusion.solver_step`` on the device): ``z``
+    and ``x0_prev`` fp32 [b,3,H,W] in place, ``y`` the bf16 [2b,H,W,8] head
+    output, ``prm`` the ``diffusion.solver_row`` of the step."""
+    b = z.shape[0]
+    HW = z.shape[-1] * z.shape[-2]
+    assert y.shape[-1] == 8 and y.shape[0] == 2 * b and y.dtype == BF16 and y.is_contiguous()
+    assert z.dtype == F32 and z.is_contiguous() and x0_prev.dtype == F32 and x0_prev.is_contiguous()
+    assert x0_prev.shape == z.shape and y.numel() == 2 * b * HW * 8 and w.numel() == b and prm.numel() >= 8
+    _chk(_lib.d3d_sampler_solve(z.data_ptr(), x0_prev.data_ptr(), y.data_ptr(), w.data_ptr(), b, HW, prm.data_ptr(),
+                                _ptr(sd), int(seed) & 0xFFFFFFFFFFFFFFFF, int(c0), _st()), "sampler_solve")
+
+
 def randn_hash(shape, seed, off, device):
     out = torch.empty(shape, dtype=F32, device=device)
     _chk(_lib.d3d_randn_hash(out.data_ptr(), out.numel(), int(seed) & 0xFFFFFFFFFFFFFFFF, int(off), _st()),

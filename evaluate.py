@@ -37,6 +37,10 @@ def parse(argv=None):
     ap.add_argument("--views", default="1,2,3", help="target views (positions in the sorted view list)")
     ap.add_argument("--w", default="3.0", help="guidance weights, one chain per object each")
     ap.add_argument("--timesteps", type=int, default=256)
+    ap.add_argument("--sampler", default="ancestral", choices=["ancestral", "ddim", "dpmpp2m"],
+                    help="update rule: the 256-step ancestral chain, DDIM or DPM-Solver++(2M) for few steps")
+    ap.add_argument("--eta", type=float, default=0.0, help="DDIM noise level in [0, 1] (1 = ancestral variance)")
+    ap.add_argument("--spacing", default="t", choices=["t", "logsnr"], help="steps uniform in t or in logSNR")
     ap.add_argument("--imgsize", type=int, default=64)
     ap.add_argument("--batch", type=int, default=64, help="objects per sampler batch")
     ap.add_argument("--autoregressive", action="store_true", help="generated views join the record")
@@ -98,7 +102,8 @@ def run(args) -> dict:
     t1 = time.time()
     rows, _ = evaluate_objects(model, objects, args.input_view, views, w, args.timesteps, args.batch,
                                args.autoregressive, args.seed, dev,
-                               on_view=write_pngs if args.save_png else None)
+                               on_view=write_pngs if args.save_png else None, solver=args.sampler, eta=args.eta,
+                               spacing=args.spacing)
     if dev.type == "cuda":
         torch.cuda.synchronize(dev)
     t2 = time.time()

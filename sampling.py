@@ -8,6 +8,8 @@ autoregressively generates each remaining view with the 256-step CFG sampler,
 one chain per guidance weight (default w = 0..7); each step conditions on a
 random already-known view of the chain (stochastic conditioning).  Writes
 ``<out>/{k}/gt.png`` and ``<out>/{k}/{i}.png`` like the reference.
+``--sampler ddim|dpmpp2m`` (with ``--eta``, ``--spacing``) swaps the ancestral
+update for a few-step solver, e.g. ``--sampler dpmpp2m --timesteps 32``.
 
 Multi-GPU: ``--gpus N`` (or torchrun) shards the guidance-weight chains over
 ranks, one process per GPU; rank 0 gathers and writes the PNGs.  ``--metrics``
@@ -36,6 +38,10 @@ def parse(argv=None):
     ap.add_argument("--out", default="sampling")
     ap.add_argument("--imgsize", type=int, default=64)
     ap.add_argument("--timesteps", type=int, default=256)
+    ap.add_argument("--sampler", default="ancestral", choices=["ancestral", "ddim", "dpmpp2m"],
+                    help="update rule: the ancestral chain, DDIM or DPM-Solver++(2M) for few steps")
+    ap.add_argument("--eta", type=float, default=0.0, help="DDIM noise level in [0, 1] (1 = ancestral variance)")
+    ap.add_argument("--spacing", default="t", choices=["t", "logsnr"], help="steps uniform in t or in logSNR")
     ap.add_argument("--w", default="0,1,2,3,4,5,6,7", help="guidance weights, one chain each")
     ap.add_argument("--max_views", type=int, default=0, help="generate at most this many views (0 = all)")
     ap.add_argument("--ema", action="store_true", help="use EMA weights when the checkpoint has them")
@@ -92,7 +98,8 @@ def run(args) -> None:
     # same seed on every rank: identical record choices, and the counter-based
     # noise is keyed by the GLOBAL chain index (chain_offset), so the gathered
     # result does not depend on the number of ranks
-    sampler = DiffusionSampler(model, args.timesteps, args.ref_quirk, seed=args.seed, device=dev, chain_offset=s)
+    sampler = DiffusionSampler(model, args.timesteps, args.ref_quirk, seed=args.seed, device=dev, chain_offset=s,
+                               solver=args.sampler, eta=args.eta, spacing=args.spacing)
     t = lambda a: torch.tensor(a, dtype=torch.float32, device=dev)  # noqa: E731
     record = [RecordEntry(t(imgs[0])[None].expand(b, -1, -1, -1).contiguous(), t(Rs[0]), t(Ts[0]))]
     if ctx.is_main:
@@ -131,7 +138,8 @@ def run(args) -> None:
             print(f"[sampling] view {k}/{nviews - 1}: {time.time() - t0:.2f}s", flush=True)
     if args.metrics and ctx.is_main:
         with open(os.path.join(args.out, "metrics.json"), "w") as f:
-            json.dump({"target": args.target, "per_image": rows}, f, indent=1, allow_nan=False)
+            json.dump({"target": args.target, "sampler": args.sampler, "eta": args.eta, "spacing": args.spacing,
+                       "per_image": rows}, f, indent=1, allow_nan=False)
     cleanup()
 
 
