@@ -27,7 +27,8 @@ from typing import Optional
 import torch
 import torch.nn as nn
 
-from ..diffusion import logsnr_schedule_cosine as _sched, q_sample as _q, diffusion_loss, cfg_posterior
+from ..diffusion import (logsnr_schedule_cosine as _sched, q_sample as _q, diffusion_loss, cfg_posterior, v_target,
+                         check_prediction)
 from ..engine.optim import FusedAdam, warmup_lr
 from ..engine.sampler import DiffusionSampler, RecordEntry
 from ..models import XUNet
@@ -37,8 +38,11 @@ from ..utils import load_checkpoint, load_model_weights
 
 class Diff3D(nn.Module):
     def __init__(self, pretrained_model: Optional[str] = None, n_samples: int = 10_000_000, image_size: int = 64,
-                 batch_size: int = 128, lr: float = 1e-4, use_scheduler: bool = False):
+                 batch_size: int = 128, lr: float = 1e-4, use_scheduler: bool = False, prediction: str = "eps"):
+        """``prediction``: what the denoiser is trained to output and the
+        sampler reads, ``"eps"`` (the reference) or ``"v"``."""
         super().__init__()
+        self.prediction = check_prediction(prediction)
         self.n_samples = n_samples
         self.batch_size = batch_size
         self.image_size = image_size
@@ -82,7 +86,7 @@ class Diff3D(nn.Module):
         img = img.to(dev)
         B = img.shape[0]
         x, z = img[:, 0], img[:, 1]
-        logsnr = self.logsnr_schedule_cosine(torch.rand(B, device=dev))
+        logsnr = self.last_logsnr = self.logsnr_schedule_cosine(torch.rand(B, device=dev))
         if noise is None:
             noise = torch.randn_like(x)
         z_noisy = self.q_sample(z, logsnr, noise)
@@ -115,7 +119,11 @@ class Diff3D(nn.Module):
         self.optimizers().zero_grad()
         noise = torch.randn_like(batch[0][:, 0].to(self.device))
         pred = self.forward(batch, noise=noise)
-        loss = diffusion_loss(noise, pred, loss_type)
+        target = noise
+        if self.prediction == "v":
+            target = v_target(batch[0][:, 1].to(self.device), self.last_logsnr, noise)
+        self.last_target = target
+        loss = diffusion_loss(target, pred, loss_type)
         self.step += 1
         if self.use_scheduler and self._sched is not None:
             self._sched.step()
@@ -135,7 +143,8 @@ class Diff3D(nn.Module):
         smp = DiffusionSampler(self.xunet_denoiser, 1, device=self.device)
         Kb = K if K.dim() == 3 else K[None].expand(b, 3, 3)
         ec, eu = smp.denoise_eps(x, z, R, T, Kb, float(logsnr))
-        return cfg_posterior(z, ec, eu, w, torch.as_tensor(logsnr), torch.as_tensor(logsnr_next))
+        return cfg_posterior(z, ec, eu, w, torch.as_tensor(logsnr), torch.as_tensor(logsnr_next),
+                             prediction=self.prediction)
 
     @torch.no_grad()
     def p_sample(self, x, z, R, T, K, logsnr, logsnr_next, w):
@@ -184,7 +193,7 @@ class Diff3D(nn.Module):
         Kb = K if K.dim() == 3 else K[None].expand(b, 3, 3).contiguous()
         wt = torch.as_tensor(w, dtype=torch.float32, device=dev).reshape(-1)
         wt = wt.expand(b).contiguous() if wt.numel() == 1 else wt
-        smp = DiffusionSampler(net, timesteps, device=dev)
+        smp = DiffusionSampler(net, timesteps, device=dev, prediction=self.prediction)
         z = torch.randn_like(x)
         imgs = []
         for k in range(timesteps):

@@ -38,6 +38,9 @@ class DiffusionConfig:
     logsnr_min: float = -20.0
     logsnr_max: float = 20.0
     loss_type: str = "l2"            # l2 | l1 | huber  (train.py:102-112)
+    prediction: str = "eps"          # eps | v  (what the model outputs; v = alpha eps - sigma x)
+    loss_weight: str = "none"        # none | min_snr  (per-example weight min(SNR, gamma) / SNR-to-target factor)
+    min_snr_gamma: float = 5.0
     cond_prob: float = 0.1           # CFG drop probability (train.py:95)
     timesteps: int = 256             # sampler steps (sampling.py:129)
     # D9: reference returns the mean (no noise) whenever logsnr_next == 0,

@@ -44,16 +44,73 @@ def q_sample(z: torch.Tensor, logsnr: torch.Tensor, noise: torch.Tensor) -> torc
     return alpha.view(shape) * z + sigma.view(shape) * noise
 
 
-def diffusion_loss(eps: torch.Tensor, eps_hat: torch.Tensor, loss_type: str = "l2") -> torch.Tensor:
+PREDICTIONS = ("eps", "v")
+LOSS_WEIGHTS = ("none", "min_snr")
+
+
+def check_prediction(prediction: str) -> str:
+    if prediction not in PREDICTIONS:
+        raise ValueError(f"prediction {prediction!r}: expected one of {PREDICTIONS}")
+    return prediction
+
+
+def check_loss_weight(loss_weight: str) -> str:
+    if loss_weight not in LOSS_WEIGHTS:
+        raise ValueError(f"loss_weight {loss_weight!r}: expected one of {LOSS_WEIGHTS}")
+    return loss_weight
+
+
+def v_target(z: torch.Tensor, logsnr: torch.Tensor, noise: torch.Tensor) -> torch.Tensor:
+    """v = alpha(l) eps - sigma(l) z for clean ``z`` and per-example logsnr [B]
+    (Salimans & Ho 2022); with z_t = q_sample: eps = sigma z_t + alpha v and
+    z = alpha z_t - sigma v."""
+    alpha, sigma = alpha_sigma(logsnr)
+    shape = (-1,) + (1,) * (z.dim() - 1)
+    return alpha.view(shape) * noise - sigma.view(shape) * z
+
+
+def min_snr_weight(logsnr: torch.Tensor, prediction: str = "eps", gamma: float = 5.0) -> torch.Tensor:
+    """min-SNR-gamma loss weight (Hang et al. 2023) per example: min(SNR, gamma)
+    divided by the factor that turns the x0 loss into the eps or v loss, in
+    forms that neither overflow nor cancel:
+        eps:  min(1, gamma e^-lambda)          v:  min(sigmoid(lambda), gamma sigmoid(-lambda))"""
+    check_prediction(prediction)
+    if prediction == "eps":
+        return torch.clamp(gamma * torch.exp(-logsnr), max=1.0)
+    return torch.minimum(torch.sigmoid(logsnr), gamma * torch.sigmoid(-logsnr))
+
+
+def diffusion_loss(eps: torch.Tensor, eps_hat: torch.Tensor, loss_type: str = "l2", *,
+                   logsnr: Optional[torch.Tensor] = None, prediction: str = "eps", loss_weight: str = "none",
+                   gamma: float = 5.0) -> torch.Tensor:
+    """mean_b[ w(lambda_b) mean_{c,p} l(eps_hat - eps) ] with ``eps`` the
+    target the model was asked for (eps or v) and ``logsnr`` [B] the examples'
+    lambda; ``loss_weight="none"`` is w = 1 (the plain mean).  The weights are
+    not normalised by their sum: micro-batches reproduce the full batch."""
+    check_prediction(prediction)
+    check_loss_weight(loss_weight)
     eps_hat = eps_hat.float()
     eps = eps.float()
+    if loss_weight == "none":
+        if loss_type == "l2":
+            return torch.mean((eps - eps_hat) ** 2)
+        if loss_type == "l1":
+            return torch.mean((eps - eps_hat).abs())
+        if loss_type == "huber":
+            return torch.nn.functional.smooth_l1_loss(eps_hat, eps)
+        raise NotImplementedError(loss_type)
+    if logsnr is None:
+        raise ValueError(f"loss_weight={loss_weight!r} needs the batch's logsnr")
     if loss_type == "l2":
-        return torch.mean((eps - eps_hat) ** 2)
-    if loss_type == "l1":
-        return torch.mean((eps - eps_hat).abs())
-    if loss_type == "huber":
-        return torch.nn.functional.smooth_l1_loss(eps_hat, eps)
-    raise NotImplementedError(loss_type)
+        el = (eps - eps_hat) ** 2
+    elif loss_type == "l1":
+        el = (eps - eps_hat).abs()
+    elif loss_type == "huber":
+        el = torch.nn.functional.smooth_l1_loss(eps_hat, eps, reduction="none")
+    else:
+        raise NotImplementedError(loss_type)
+    wgt = min_snr_weight(logsnr.reshape(-1).float(), prediction, gamma)
+    return torch.mean(wgt.view((-1,) + (1,) * (el.dim() - 1)) * el)
 
 
 SPACINGS = ("t", "logsnr")
@@ -75,11 +132,21 @@ def sampler_logsnrs(timesteps: int, logsnr_min: float = -20.0, logsnr_max: float
     return lam[:-1], lam[1:]
 
 
+def _x0(z, out, alpha, sigma, prediction: str):
+    """Clamped data prediction from the guided model output."""
+    if prediction == "eps":
+        return ((z - sigma * out) / alpha).clamp(-1.0, 1.0)
+    return (alpha * z - sigma * out).clamp(-1.0, 1.0)
+
+
 def cfg_posterior(z: torch.Tensor, eps_cond: torch.Tensor, eps_uncond: torch.Tensor,
-                  w: torch.Tensor, logsnr: torch.Tensor, logsnr_next: torch.Tensor
+                  w: torch.Tensor, logsnr: torch.Tensor, logsnr_next: torch.Tensor, prediction: str = "eps"
                   ) -> Tuple[torch.Tensor, torch.Tensor]:
     """Classifier-free-guided DDPM posterior mean / variance (reference math,
-    `train.py:140-166`).  ``w`` is per-example [b]; logsnr scalars."""
+    `train.py:140-166`).  ``w`` is per-example [b]; logsnr scalars.  With
+    ``prediction="v"`` the two model outputs are v and the guided one gives
+    x0 = clamp(alpha z - sigma v, -1, 1); everything after x0 is the same."""
+    check_prediction(prediction)
     shape = (-1,) + (1,) * (z.dim() - 1)
     w = w.to(z.dtype).view(shape)
     logsnr = torch.as_tensor(logsnr, dtype=z.dtype, device=z.device)
@@ -88,7 +155,7 @@ def cfg_posterior(z: torch.Tensor, eps_cond: torch.Tensor, eps_uncond: torch.Ten
     alpha, sigma = alpha_sigma(logsnr)
     alpha_next = torch.sigmoid(logsnr_next).sqrt()
     eps = (1.0 + w) * eps_cond - w * eps_uncond
-    x0 = ((z - sigma * eps) / alpha).clamp(-1.0, 1.0)
+    x0 = _x0(z, eps, alpha, sigma, prediction)
     mean = alpha_next * (z * (1.0 - c) / alpha + c * x0)
     var = torch.sigmoid(-logsnr_next) * c
     return mean, var
@@ -97,8 +164,8 @@ def cfg_posterior(z: torch.Tensor, eps_cond: torch.Tensor, eps_uncond: torch.Ten
 # ------------------------------------------------------- few-step solvers
 # One step lambda -> lambda' of every solver is the linear update
 #     z' = kz z + k0 x0 + k1 x0_prev + kn N(0,1),
-# x0 = clamp((z - sigma eps)/alpha, -1, 1) the guided data prediction and
-# x0_prev the previous step's.  With h = (lambda' - lambda)/2 and
+# x0 = clamp((z - sigma eps)/alpha, -1, 1) the guided data prediction (v-prediction:
+# clamp(alpha z - sigma v, -1, 1)) and x0_prev the previous step's.  With h = (lambda' - lambda)/2 and
 # c = -expm1(lambda - lambda'):
 #   ddim (eta in [0,1]):  s = eta sigma' sqrt(c) (0 on the last step),
 #       g = sqrt(sigma'^2 - s^2)/sigma;  kz = g, k0 = alpha' - g alpha, kn = s
@@ -152,17 +219,19 @@ def solver_row(lam: Sequence[float], lam_next: Sequence[float], k: int, solver: 
 
 
 def solver_step(z: torch.Tensor, eps_cond: torch.Tensor, eps_uncond: torch.Tensor, w: torch.Tensor,
-                x0_prev: Optional[torch.Tensor], row, noise: Optional[torch.Tensor]
+                x0_prev: Optional[torch.Tensor], row, noise: Optional[torch.Tensor], prediction: str = "eps"
                 ) -> Tuple[torch.Tensor, torch.Tensor]:
     """One solver step in the dtype of ``z``: ``(z', x0)`` from a
     ``solver_row`` (8 floats or a tensor of them).  ``x0_prev`` is read only
     when the row's k1 != 0, ``noise`` only when kn != 0 (either may be None
-    otherwise); the returned clamped x0 is the next step's ``x0_prev``."""
+    otherwise); the returned clamped x0 is the next step's ``x0_prev``.
+    ``prediction="v"``: the model outputs are v (see :func:`cfg_posterior`)."""
+    check_prediction(prediction)
     _, alpha, sigma, kz, k0, k1, kn = (float(v) for v in row[:7])
     shape = (-1,) + (1,) * (z.dim() - 1)
     w = w.to(z.dtype).view(shape)
     eps = (1.0 + w) * eps_cond - w * eps_uncond
-    x0 = ((z - sigma * eps) / alpha).clamp(-1.0, 1.0)
+    x0 = _x0(z, eps, alpha, sigma, prediction)
     out = kz * z + k0 * x0
     if k1 != 0.0:
         out = out + k1 * x0_prev.to(z.dtype)

@@ -37,7 +37,9 @@ def validation_seed(seed: int, i: int) -> int:
 def heldout_loss(model, batches: Iterable, seed: int, diffusion_cfg, dtype) -> torch.Tensor:
     """Mean training loss (``ops.diffusion_inputs`` -> forward ->
     ``ops.diff_loss_nhwc``) of ``model`` in eval mode over ``batches`` of
-    (img [B,2,3,H,W], R, T, K) on the model's device, batch i drawn with
+    (img [B,2,3,H,W], R, T, K) on the model's device -- the configured
+    objective: the target of ``diffusion_cfg.prediction`` under its
+    ``loss_weight`` -- batch i drawn with
     ``validation_seed(seed, i)``.  Returns a device scalar; the model's
     train / eval mode is restored, nothing else is touched."""
     dc = diffusion_cfg
@@ -47,9 +49,11 @@ def heldout_loss(model, batches: Iterable, seed: int, diffusion_cfg, dtype) -> t
     try:
         for i, (img, R, T, K) in enumerate(batches):
             xz, eps, logsnr, keep = ops.diffusion_inputs(img, validation_seed(seed, i), 0, dc.cond_prob,
-                                                         dc.logsnr_min, dc.logsnr_max, dtype)
+                                                         dc.logsnr_min, dc.logsnr_max, dtype,
+                                                         prediction=dc.prediction)
             y = model({"xz": xz, "logsnr": logsnr, "R": R, "t": T, "K": K}, cond_mask=keep, head_nhwc=True)
-            loss = ops.diff_loss_nhwc(y, eps, dc.loss_type).detach().float()
+            loss = ops.diff_loss_nhwc(y, eps, dc.loss_type, logsnr=logsnr, prediction=dc.prediction,
+                                      loss_weight=dc.loss_weight, gamma=dc.min_snr_gamma).detach().float()
             total = loss if total is None else total + loss
             n += 1
     finally:
@@ -104,7 +108,7 @@ def evaluate_objects(model, objects: Sequence[EvalObject], input_view: int = 0, 
                      autoregressive: bool = False, seed: int = 0, device=None, ref_quirk: bool = False,
                      graph: Optional[bool] = None, keep_images: bool = False,
                      on_view: Optional[Callable] = None, solver: str = "ancestral", eta: float = 0.0,
-                     spacing: str = "t"):
+                     spacing: str = "t", prediction: str = "eps"):
     """Generate ``views`` of every object from its ``input_view`` and score
     them.  Returns ``(rows, images)``: one row ``{instance, view, w, chain,
     mse, psnr, ssim}`` per (object, view, w) -- ``chain`` the global chain
@@ -113,7 +117,8 @@ def evaluate_objects(model, objects: Sequence[EvalObject], input_view: int = 0, 
     [len(w),3,H,W] batch on the CPU.  ``on_view(objects, view, out, gt)`` is
     called with each generated batch ([G * len(w),3,H,W], object-major) and
     its ground truth [G,3,H,W].  ``solver`` / ``eta`` / ``spacing``: the
-    update rule and step spacing of :class:`DiffusionSampler`."""
+    update rule and step spacing of :class:`DiffusionSampler`, ``prediction``
+    what the model outputs (eps or v)."""
     dev = torch.device(device) if device is not None else next(model.parameters()).device
     nw = len(w)
     rows: List[dict] = []
@@ -123,7 +128,7 @@ def evaluate_objects(model, objects: Sequence[EvalObject], input_view: int = 0, 
         G = len(objs)
         # chains are object-major and numbered globally, so a row (and its noise) does not depend on `batch`
         smp = DiffusionSampler(model, timesteps, ref_quirk, seed=seed, device=dev, chain_offset=s * nw, graph=graph,
-                               solver=solver, eta=eta, spacing=spacing)
+                               solver=solver, eta=eta, spacing=spacing, prediction=prediction)
         group = torch.arange(G).repeat_interleave(nw)
         wv = torch.tensor([float(x) for x in w]).repeat(G)
         K = torch.stack([o.K for o in objs]).to(dev)
@@ -167,6 +172,16 @@ def summarize(rows: Sequence[dict]) -> dict:
 
 
 # ------------------------------------------------------------------ loading
+def resolve_prediction(choice: str, cfg) -> str:
+    """The ``--prediction`` of the sampling CLIs: ``auto`` reads the
+    checkpoint's ``config.diffusion.prediction`` (``cfg`` None -- a checkpoint
+    without a config, such as a reference checkpoint -- means eps)."""
+    from ..diffusion import check_prediction
+    if choice == "auto":
+        choice = cfg.diffusion.prediction if cfg is not None else "eps"
+    return check_prediction(choice)
+
+
 def load_model(path: str, imgsize: int, device, ema: bool = False):
     """The model of a checkpoint, as ``sampling.py`` loads it: our checkpoints
     carry their config, reference checkpoints (with or without ``module.``)

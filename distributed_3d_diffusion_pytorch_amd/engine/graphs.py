@@ -255,8 +255,7 @@ class GraphedTrainStep:
             _xunet.PARAM_FENCE[0] = None
         if defer:
             main.wait_stream(self.upd_stream)
-        from .. import ops
-        loss = ops.diff_loss_nhwc(y, eps, tr.cfg.diffusion.loss_type)
+        loss = tr.loss(y, eps, batch["logsnr"])
         (loss * self.frac).backward()
         self.loss_acc.add_(loss.detach() * self.frac)
         if red is not None and comm:

@@ -47,6 +47,7 @@ from typing import List, Optional, Tuple
 import torch
 
 from ..diffusion import (logsnr_schedule_cosine, sampler_logsnrs, cfg_posterior, solver_row, solver_step, SOLVERS,
+                         check_prediction,
                          SPACINGS)
 
 _M64 = (1 << 64) - 1
@@ -73,7 +74,7 @@ class DiffusionSampler:
     def __init__(self, model: torch.nn.Module, timesteps: int = 256, ref_quirk: bool = False,
                  logsnr_min: float = -20.0, logsnr_max: float = 20.0, seed: int = 0, device=None,
                  chain_offset: int = 0, graph: Optional[bool] = None, share_cond: bool = True, *,
-                 solver: str = "ancestral", eta: float = 0.0, spacing: str = "t"):
+                 solver: str = "ancestral", eta: float = 0.0, spacing: str = "t", prediction: str = "eps"):
         """``chain_offset``: global index of this sampler's first chain (its
         rank's shard start).  ``graph``: replay the step from a HIP graph
         (default: on for the bf16 HIP path).  ``share_cond``: compute the
@@ -84,7 +85,9 @@ class DiffusionSampler:
         ``eta`` in [0, 1]: 0 deterministic, 1 the ancestral variance) or
         ``"dpmpp2m"`` (DPM-Solver++ 2M, deterministic) -- the update rules of
         ``diffusion.solver_row``; ``spacing``: the steps uniform in ``"t"`` on
-        the cosine schedule or uniform in ``"logsnr"``.
+        the cosine schedule or uniform in ``"logsnr"``.  ``prediction``: what the
+        model outputs, ``"eps"`` or ``"v"`` (x0 = clamp(alpha z - sigma v)); it
+        must be what the model was trained with.
 
         A multistep solver keeps the previous step's data prediction.  With
         stochastic conditioning and more than one record entry that prediction
@@ -100,6 +103,7 @@ class DiffusionSampler:
             raise ValueError("dpmpp2m is deterministic: eta must be 0")
         if ref_quirk and solver != "ancestral":
             raise ValueError("ref_quirk is a property of the ancestral chain: solver must be 'ancestral'")
+        self.prediction = check_prediction(prediction)
         self.solver, self.eta, self.spacing = solver, float(eta), spacing
         self.share_cond = bool(share_cond)
         self.model = model
@@ -242,11 +246,13 @@ class DiffusionSampler:
             row = self.solver_params(k, first_order=x0_prev is None)
             noise = self._noise(TI.K_NZ, k, tuple(z.shape), z.device) if row[6] != 0.0 else None
             # (the fp32 row the device table holds, so the CPU and the HIP path take the same step)
-            z, x0 = solver_step(z, eps_c, eps_u, w, x0_prev, torch.tensor(row, dtype=torch.float32), noise)
+            z, x0 = solver_step(z, eps_c, eps_u, w, x0_prev, torch.tensor(row, dtype=torch.float32), noise,
+                                prediction=self.prediction)
             if state is not None:
                 state.x0_prev = x0
             return z
-        mean, var = cfg_posterior(z, eps_c, eps_u, w, torch.tensor(self.lam[k]), torch.tensor(self.lam_next[k]))
+        mean, var = cfg_posterior(z, eps_c, eps_u, w, torch.tensor(self.lam[k]), torch.tensor(self.lam_next[k]),
+                                  prediction=self.prediction)
         if not self.add_noise(k):
             return mean
         return mean + var.sqrt() * self._noise(TI.K_NZ, k, tuple(z.shape), z.device)
@@ -292,9 +298,11 @@ class DiffusionSampler:
                      "K": torch.cat([K, K])}
             y = self.model(batch, cond_mask=mask, head_nhwc=True)
         if ancestral:
-            hip_impl.sampler_step2(z, y, w.float().contiguous(), prm, None, self.step_seed(k), self.c0)
+            hip_impl.sampler_step2(z, y, w.float().contiguous(), prm, None, self.step_seed(k), self.c0,
+                                   prediction=self.prediction)
             return z
-        hip_impl.sampler_solve(z, x0_prev, y, w.float().contiguous(), prm, None, self.step_seed(k), self.c0)
+        hip_impl.sampler_solve(z, x0_prev, y, w.float().contiguous(), prm, None, self.step_seed(k), self.c0,
+                               prediction=self.prediction)
         if state is not None:
             state.x0_prev = x0_prev
         return z
@@ -347,9 +355,11 @@ class DiffusionSampler:
         solver has k1 = 0, so the history restarts with each run."""
         from ..ops import hip_impl
         if self.solver == "ancestral":
-            hip_impl.sampler_step2(g["z"], y, g["w"], g["prm"], g["sd"], self.seed_base, self.c0)
+            hip_impl.sampler_step2(g["z"], y, g["w"], g["prm"], g["sd"], self.seed_base, self.c0,
+                                   prediction=self.prediction)
         else:
-            hip_impl.sampler_solve(g["z"], g["x0"], y, g["w"], g["prm"], g["sd"], self.seed_base, self.c0)
+            hip_impl.sampler_solve(g["z"], g["x0"], y, g["w"], g["prm"], g["sd"], self.seed_base, self.c0,
+                                   prediction=self.prediction)
 
     def _capture(self, g: dict, body) -> dict:
         """Warm ``body`` up on a side stream, capture it into ``g["graph"]``

@@ -27,8 +27,9 @@ from .. import ops
 from ..config import TrainConfig, dumps, to_dict
 from ..models import XUNet
 from ..parallel import (DistContext, FlatParams, GradReducer, get_context, check_replicas_in_sync)
+from ..diffusion import check_prediction, check_loss_weight
 from ..utils import (save_checkpoint, load_checkpoint, load_model_weights, find_resume, MetricsLogger,
-                     StepTimer, train_flops_per_example, range_push, check_finite)
+                     checkpoint_prediction, StepTimer, train_flops_per_example, range_push, check_finite)
 from .optim import FusedAdam, ema_decay_for, warmup_lr
 
 
@@ -59,6 +60,8 @@ class Trainer:
             self.tuned_gemms = enable_tuned_gemms()
         if cfg.deterministic:
             torch.use_deterministic_algorithms(True, warn_only=True)
+        check_prediction(cfg.diffusion.prediction)
+        check_loss_weight(cfg.diffusion.loss_weight)
         torch.manual_seed(cfg.seed)
         self.model = XUNet(copy.deepcopy(cfg.model)).to(dev)
         self.dtype = torch.bfloat16 if (dev.type == "cuda" and cfg.dtype == "bf16") else torch.float32
@@ -132,6 +135,8 @@ class Trainer:
         self.epoch_pos = 0          # batches of self.epoch already consumed (mid-epoch resume)
         if cfg.pretrained and not cfg.transfer:
             ck = load_checkpoint(cfg.pretrained, map_location="cpu")
+            if "optim" in ck:
+                self._check_objective(ck, cfg.pretrained)
             load_model_weights(self.model, ck["model"])
             if "optim" in ck:
                 self.optim.load_state_dict(ck["optim"])
@@ -142,11 +147,21 @@ class Trainer:
             self.reducer.broadcast_params(0)
 
     # ------------------------------------------------------------------
+    def _check_objective(self, ck: dict, path: str) -> None:
+        """Continuing a run (weights plus optimizer state) must not silently
+        switch what the model is trained to output."""
+        stored = checkpoint_prediction(ck)
+        mine = self.cfg.diffusion.prediction
+        if stored != mine:
+            raise ValueError(f"checkpoint {path} was trained with diffusion.prediction={stored!r} but this run is "
+                             f"configured with diffusion.prediction={mine!r}: refusing to switch objectives")
+
     def resume(self, transfer: str) -> bool:
         path = find_resume(transfer)
         if path is None:
             return False
         ck = load_checkpoint(path, map_location="cpu")
+        self._check_objective(ck, path)
         load_model_weights(self.model, ck["model"])
         if "optim" in ck:
             self.optim.load_state_dict(ck["optim"])
@@ -226,7 +241,8 @@ class Trainer:
         graph replay see exactly the numbers of the full-batch eager step."""
         dc = self.cfg.diffusion
         xz, eps, logsnr, keep = ops.diffusion_inputs(img, self.step_seed(step_word), e0, dc.cond_prob,
-                                                     dc.logsnr_min, dc.logsnr_max, self.dtype)
+                                                     dc.logsnr_min, dc.logsnr_max, self.dtype,
+                                                     prediction=dc.prediction)
         batch = {"xz": xz, "logsnr": logsnr, "R": R, "t": T, "K": K}
         return batch, keep, eps
 
@@ -234,7 +250,14 @@ class Trainer:
         batch, mask, eps = self.diffusion_inputs(img, R, T, K, e0)
         self.model.set_dropout_seed(dropout_word(self.step * self.ctx.world + self.ctx.rank, chunk))
         y = self.model(batch, cond_mask=mask, head_nhwc=True)
-        return ops.diff_loss_nhwc(y, eps, self.cfg.diffusion.loss_type)
+        return self.loss(y, eps, batch["logsnr"])
+
+    def loss(self, y, target, logsnr) -> torch.Tensor:
+        """The configured objective on the NHWC head output: ``target`` (eps or
+        v) and ``logsnr`` [B,2] are those of :meth:`diffusion_inputs`."""
+        dc = self.cfg.diffusion
+        return ops.diff_loss_nhwc(y, target, dc.loss_type, logsnr=logsnr, prediction=dc.prediction,
+                                  loss_weight=dc.loss_weight, gamma=dc.min_snr_gamma)
 
     last_grad_norm: Optional[torch.Tensor] = None    # device scalar, set when measured / clipping
     last_allreduce_ms: float = 0.0

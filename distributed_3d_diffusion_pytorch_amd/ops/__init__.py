@@ -138,18 +138,24 @@ def attention(qkv, heads: int, cross: bool):
 
 
 def diffusion_inputs(img, seed: int, e0: int = 0, cond_prob: float = 0.1, logsnr_min: float = -20.0,
-                     logsnr_max: float = 20.0, dtype=torch.float32):
+                     logsnr_max: float = 20.0, dtype=torch.float32, prediction: str = "eps"):
     """Counter-based training-input draw (see torch_impl.diffusion_inputs);
-    one HIP launch for bf16 GPU runs."""
+    one HIP launch for bf16 GPU runs.  Slot 1 of the result is the loss target
+    of ``prediction`` (eps, or v = alpha eps - sigma z_clean)."""
     if dtype == torch.bfloat16 and img.is_cuda and use_hip(img, any_dtype=True):
-        return _h().diffusion_inputs(img, seed, e0, cond_prob, logsnr_min, logsnr_max, dtype)
-    return _t.diffusion_inputs(img, seed, e0, cond_prob, logsnr_min, logsnr_max, dtype)
+        return _h().diffusion_inputs(img, seed, e0, cond_prob, logsnr_min, logsnr_max, dtype, prediction=prediction)
+    return _t.diffusion_inputs(img, seed, e0, cond_prob, logsnr_min, logsnr_max, dtype, prediction=prediction)
 
 
-def diff_loss_nhwc(y, eps, loss_type: str = "l2"):
+def diff_loss_nhwc(y, target, loss_type: str = "l2", *, logsnr=None, prediction: str = "eps",
+                   loss_weight: str = "none", gamma: float = 5.0):
+    """mean_b[ w(lambda_b) mean_{c,p} l(y - target) ] on the NHWC head output;
+    ``logsnr`` is the [B,2] tensor of :func:`diffusion_inputs` (column 1 is
+    read), required unless ``loss_weight="none"`` (see torch_impl.diff_loss_nhwc)."""
+    kw = dict(logsnr=logsnr, prediction=prediction, loss_weight=loss_weight, gamma=gamma)
     if use_hip(y):
-        return _h().diff_loss_nhwc(y, eps, loss_type)
-    return _t.diff_loss_nhwc(y, eps, loss_type)
+        return _h().diff_loss_nhwc(y, target, loss_type, **kw)
+    return _t.diff_loss_nhwc(y, target, loss_type, **kw)
 
 
 def avgpool2(x):

@@ -54,14 +54,14 @@ SIGNATURES = {
     "d3d_add_scale": [P, P, P, F, L, P],
     "d3d_set_words": [P, I, F, F, F, F, F, F, F, F, P],
     "d3d_add_scale_gn": [P, P, P, F, L, I, I, I, P, P],
-    "d3d_sampler_step": [P, P, P, P, P, I, I, F, F, F, F, F, I, U64, P],
+    "d3d_sampler_step": [P, P, P, P, P, I, I, F, F, F, F, F, I, U64, I, P],
     "d3d_sampler_inputs": [P, P, I, I, P, P, U64, L, P, P, P],
-    "d3d_sampler_step2": [P, P, P, I, I, P, P, U64, L, P],
-    "d3d_sampler_solve": [P, P, P, P, I, I, P, P, U64, L, P],
+    "d3d_sampler_step2": [P, P, P, I, I, P, P, U64, L, I, P],
+    "d3d_sampler_solve": [P, P, P, P, I, I, P, P, U64, L, I, P],
     "d3d_randn_hash": [P, L, U64, L, P],
-    "d3d_diffusion_fwd2": [P, I, I, U64, P, L, F, F, F, P, P, P, P, P],
-    "d3d_diff_loss": [P, P, I, I, I, I, P, P, P],
-    "d3d_diff_loss_bwd": [P, P, P, I, I, I, I, P, P],
+    "d3d_diffusion_fwd2": [P, I, I, U64, P, L, F, F, F, P, P, P, P, I, P],
+    "d3d_diff_loss": [P, P, I, I, I, I, P, P, P, I, F, P],
+    "d3d_diff_loss_bwd": [P, P, P, I, I, I, I, P, P, I, F, P],
     # adam.hip
     "d3d_adam": [P, P, P, P, P, L, F, F, F, F, F, F, F, F, P],
     "d3d_adam_dev": [P, P, P, P, P, L, P, P],

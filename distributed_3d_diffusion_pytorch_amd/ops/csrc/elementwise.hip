@@ -186,6 +186,19 @@ __global__ void __launch_bounds__(256) add_scale_gn_k(const bf16* a, const bf16*
 // CFG ancestral step for fp32 z [b, D]:
 //   eps = (1+w) ec - w eu;  x0 = clamp((z - sigma eps)/alpha, -1, 1)
 //   mean = alpha_n (z (1-c)/alpha + c x0);  z' = mean + sqrt(var) * N(0,1) * add_noise
+// PRED selects what the model outputs (a compile-time switch on every sampler
+// kernel): 0 = eps as above, 1 = v with x0 = clamp(alpha z - sigma v, -1, 1);
+// CFG is linear in either output, so the guided combination is the same.
+template <int PRED>
+__device__ __forceinline__ float pred_x0(float zi, float e, float alpha, float sigma) {
+  if constexpr (PRED == 0) {
+    return fminf(fmaxf((zi - sigma * e) / alpha, -1.f), 1.f);
+  } else {
+    return fminf(fmaxf(alpha * zi - sigma * e, -1.f), 1.f);
+  }
+}
+
+template <int PRED>
 __global__ void sampler_step_k(const float* __restrict__ z, const float* __restrict__ ec,
                                const float* __restrict__ eu, const float* __restrict__ w, float* __restrict__ out,
                                int D, long total, float alpha, float sigma, float alpha_n, float c, float var_sqrt,
@@ -195,7 +208,7 @@ __global__ void sampler_step_k(const float* __restrict__ z, const float* __restr
     float wb = w[b];
     float e = (1.f + wb) * ec[i] - wb * eu[i];
     float zi = z[i];
-    float x0 = fminf(fmaxf((zi - sigma * e) / alpha, -1.f), 1.f);
+    float x0 = pred_x0<PRED>(zi, e, alpha, sigma);
     float m = alpha_n * (zi * (1.f - c) / alpha + c * x0);
     if (add_noise) m += var_sqrt * normal01(seed, (uint64_t)i);
     out[i] = m;
@@ -242,12 +255,23 @@ __global__ void sampler_inputs_k(const float* __restrict__ xc, const float* __re
 // Ancestral CFG step reading eps straight from the padded NHWC head output
 // y [2b,H,W,8] bf16 (rows [0,b) conditional, [b,2b) unconditional); z fp32
 // [b,3,H,W] updated in place.
+template <int PRED>
 __global__ void sampler_step2_k(float* __restrict__ z, const bf16* __restrict__ y, const float* __restrict__ w,
                                 int b, int HW, const float* __restrict__ prm, const uint64_t* __restrict__ sd,
                                 uint64_t seed, long c0) {
   const uint64_t s = seed + (sd ? sd[0] : 0ull) * 0x9E3779B97F4A7C15ull;
   const float alpha = prm[1], sigma = prm[2], alpha_n = prm[3], c = prm[4], var_sqrt = prm[5];
   const bool noise = prm[6] != 0.f;
+  // 1 - c = exp(lambda - lambda_next).  At the first steps c is within an ulp of
+  // 1 and the fp32 difference has lost its digits (the eps form's x0 is just as
+  // ill conditioned there).  The v form holds those steps, so it takes 1 - c
+  // from the row's other entries with no cancellation:
+  //   1 - c = (alpha / sigma)^2 sigma_next^2 / alpha_next^2,  sigma_next^2 = var / c
+  float omc = 1.f - c;
+  if constexpr (PRED == 1) {
+    const float as = alpha / sigma;
+    omc = as * as * (var_sqrt * var_sqrt) / (c * alpha_n * alpha_n);
+  }
   GRID_LOOP(i, (long)b * 3 * HW) {
     const int j = (int)(i / (3 * HW));
     const int r = (int)(i - (long)j * 3 * HW);
@@ -257,8 +281,8 @@ __global__ void sampler_step2_k(float* __restrict__ z, const bf16* __restrict__ 
     const float wb = w[j];
     const float e = (1.f + wb) * ec - wb * eu;
     const float zi = z[i];
-    const float x0 = fminf(fmaxf((zi - sigma * e) / alpha, -1.f), 1.f);
-    float m = alpha_n * (zi * (1.f - c) / alpha + c * x0);
+    const float x0 = pred_x0<PRED>(zi, e, alpha, sigma);
+    float m = alpha_n * (zi * omc / alpha + c * x0);
     if (noise) m += var_sqrt * normal01(s ^ K_NZ, (uint64_t)(c0 + j) * 3 * HW + r);
     z[i] = m;
   }
@@ -268,6 +292,7 @@ __global__ void sampler_step2_k(float* __restrict__ z, const bf16* __restrict__ 
 // every solver is one linear update with host-computed coefficients,
 //   prm = [lambda, alpha, sigma, kz, k0, k1, kn, lambda0]
 //   eps = (1+w) ec - w eu;  x0 = clamp((z - sigma eps)/alpha, -1, 1)
+//   (PRED 1: v = (1+w) vc - w vu;  x0 = clamp(alpha z - sigma v, -1, 1))
 //   z' = kz z + k0 x0 + k1 x0_prev + kn N(0,1);  x0_prev' = x0
 // One thread per (chain, pixel): the conditional and the unconditional head
 // row y [2b,H,W,8] bf16 are one 16-byte load each, the three channel planes of
@@ -275,6 +300,7 @@ __global__ void sampler_step2_k(float* __restrict__ z, const bf16* __restrict__ 
 // x0_prev is read only when k1 != 0 (a fresh history buffer may hold anything)
 // and the noise -- same key and index as sampler_step2_k -- is drawn only when
 // kn != 0; both branches are uniform.
+template <int PRED>
 __global__ void sampler_solve_k(float* __restrict__ z, float* __restrict__ x0p, const bf16* __restrict__ y,
                                 const float* __restrict__ w, int b, int HW, const float* __restrict__ prm,
                                 const uint64_t* __restrict__ sd, uint64_t seed, long c0) {
@@ -293,7 +319,7 @@ __global__ void sampler_solve_k(float* __restrict__ z, float* __restrict__ x0p, 
       const size_t e = (size_t)j * 3 * HW + r;
       const float eps = (1.f + wb) * ec[ch] - wb * eu[ch];
       const float zi = z[e];
-      const float x0 = fminf(fmaxf((zi - sigma * eps) / alpha, -1.f), 1.f);
+      const float x0 = pred_x0<PRED>(zi, eps, alpha, sigma);
       float m = kz * zi + k0 * x0;
       if (hist) m += k1 * x0p[e];
       if (noise) m += kn * normal01(s ^ K_NZ, (uint64_t)(c0 + j) * 3 * HW + r);
@@ -315,13 +341,16 @@ __global__ void randn_hash_k(float* __restrict__ out, long n, uint64_t seed, lon
 //   t_g    = u01(s, 4g)                 lambda = -2 log tan(a t + b)
 //   keep_g = u01(s, 4g + 1) > cond_prob
 //   eps    = N(s ^ K_EPS, g*3HW + c*HW + p)   x_noise = N(s ^ K_XN, same index)
-// Outputs: eps [B,3,H,W] fp32 (loss target), logsnr [B,2] (frame 0 = lambda(0)),
-// keep [B] u8, and the stem input xz [2B,H,W,8] bf16 (frame 0 = keep ? x :
-// x_noise, frame 1 = alpha z + sigma eps, channels 3..7 zero).
+// Outputs: the loss target [B,3,H,W] fp32 (PRED 0: eps; PRED 1: v = alpha eps -
+// sigma z, z the clean target frame), logsnr [B,2] (frame 0 = lambda(0)), keep
+// [B] u8, and the stem input xz [2B,H,W,8] bf16 (frame 0 = keep ? x : x_noise,
+// frame 1 = alpha z + sigma eps, channels 3..7 zero); only the target depends
+// on PRED.
 // Graph replays pass seed_dev = the step's device seed block [dropout word,
 // draw word, example offset]: s = seed + sd[1] * golden, e0 += sd[2].
 #define K_EPS 0x5851F42D4C957F2Dull
 #define K_XN 0x14057B7EF767814Full
+template <int PRED>
 __global__ void diffusion_fwd2_k(const float* __restrict__ img, int B, int HW, uint64_t seed,
                                  const uint64_t* __restrict__ seed_dev, long e0, float cond_prob, float a, float b0,
                                  float* __restrict__ eps_out, float* __restrict__ logsnr_out,
@@ -349,9 +378,10 @@ __global__ void diffusion_fwd2_k(const float* __restrict__ img, int B, int HW, u
     for (int c = 0; c < 3; ++c) {
       const uint64_t idx = g * 3 * (uint64_t)HW + (uint64_t)c * HW + p;
       const float e = normal01(s ^ K_EPS, idx);
-      eps_out[(size_t)bb * 3 * HW + (size_t)c * HW + p] = e;
+      const float zc = z[(size_t)c * HW + p];
+      eps_out[(size_t)bb * 3 * HW + (size_t)c * HW + p] = PRED == 0 ? e : alpha * e - sigma * zc;
       ox[c] = (bf16)(keep ? x[(size_t)c * HW + p] : normal01(s ^ K_XN, idx));
-      oz[c] = (bf16)(alpha * z[(size_t)c * HW + p] + sigma * e);
+      oz[c] = (bf16)(alpha * zc + sigma * e);
     }
     *reinterpret_cast<bf16x8*>(xz + ((size_t)2 * bb * HW + p) * 8) = ox;
     *reinterpret_cast<bf16x8*>(xz + ((size_t)(2 * bb + 1) * HW + p) * 8) = oz;
@@ -367,21 +397,53 @@ __global__ void diffusion_fwd2_k(const float* __restrict__ img, int B, int HW, u
 // channels valid) against eps [B,3,H,W] fp32: per-block partial sums over a
 // fixed grid (deterministic), then one block sums the partials in order.
 // mode 0: mean (y - eps)^2, 1: mean |y - eps|.
+// WM is the per-example loss weight, a function of logsnr[2 b + 1] = lambda_b
+// (min-SNR-gamma, in forms that neither overflow nor cancel):
+//   0: none (logsnr is not read)
+//   1: eps target, w = min(1, gamma e^-lambda)
+//   2: v target,   w = min(sigmoid(lambda), gamma sigmoid(-lambda))
+// applied to the element loss (forward) and to dy (backward); the weights are
+// not normalised, so the mean stays over B*3*HW.
+template <int WM>
+__device__ __forceinline__ float loss_weight(const float* __restrict__ logsnr, int bb, float gamma) {
+  if constexpr (WM == 0) {
+    return 1.f;
+  } else {
+    const float lam = logsnr[2 * bb + 1];
+    if constexpr (WM == 1) {
+      return fminf(1.f, gamma * expf(-lam));
+    } else {
+      const float en = expf(-fabsf(lam));  // sigmoid(+-lambda) without overflow
+      const float hi = 1.f / (1.f + en), lo = en / (1.f + en);
+      return lam >= 0.f ? fminf(hi, gamma * lo) : fminf(lo, gamma * hi);
+    }
+  }
+}
+
 #define LOSS_BLOCKS 256
+template <int WM>
 __global__ void __launch_bounds__(256) diff_loss_part_k(const bf16* __restrict__ y, const float* __restrict__ eps,
-                                                        int B, int HW, int CP, int mode, float* __restrict__ part) {
+                                                        int B, int HW, int CP, int mode,
+                                                        const float* __restrict__ logsnr, float gamma,
+                                                        float* __restrict__ part) {
   float acc = 0.f;
   const long n = (long)B * HW;
   GRID_LOOP(i, n) {
     const int bb = (int)(i / HW);
     const int p = (int)(i - (long)bb * HW);
     const bf16* yp = y + (size_t)i * CP;
+    [[maybe_unused]] const float wgt = loss_weight<WM>(logsnr, bb, gamma);
 #pragma unroll
     for (int c = 0; c < 3; ++c) {
       const float d = (float)yp[c] - eps[(size_t)bb * 3 * HW + (size_t)c * HW + p];
       // 0: l2, 1: l1, 2: huber = smooth_l1 with beta 1 (F.smooth_l1_loss, train.py:108-109)
       const float ad = fabsf(d);
-      acc += mode == 0 ? d * d : (mode == 1 ? ad : (ad < 1.f ? 0.5f * d * d : ad - 0.5f));
+      const float l = mode == 0 ? d * d : (mode == 1 ? ad : (ad < 1.f ? 0.5f * d * d : ad - 0.5f));
+      if constexpr (WM == 0) {
+        acc += l;
+      } else {
+        acc += wgt * l;
+      }
     }
   }
   __shared__ float red[4];
@@ -404,13 +466,15 @@ __global__ void __launch_bounds__(256) diff_loss_final_k(const float* __restrict
 
 // dy [B,H,W,CP] bf16 = dL * d/dy loss (channels >= 3 zero); dL read from the
 // device (the upstream gradient of the scalar loss, e.g. a micro-batch weight).
+template <int WM>
 __global__ void diff_loss_bwd_k(const bf16* __restrict__ y, const float* __restrict__ eps,
                                 const float* __restrict__ dloss, int B, int HW, int CP, int mode, float inv_n,
-                                bf16* __restrict__ dy) {
-  const float g = dloss[0] * inv_n;
+                                const float* __restrict__ logsnr, float gamma, bf16* __restrict__ dy) {
+  const float g0 = dloss[0] * inv_n;
   GRID_LOOP(i, (long)B * HW) {
     const int bb = (int)(i / HW);
     const int p = (int)(i - (long)bb * HW);
+    const float g = WM == 0 ? g0 : g0 * loss_weight<WM>(logsnr, bb, gamma);
     const bf16* yp = y + (size_t)i * CP;
     bf16x8 o;
 #pragma unroll
@@ -507,9 +571,10 @@ D3D_API int d3d_add_scale(const void* a, const void* b, void* y, float s, long n
 }
 D3D_API int d3d_sampler_step(const float* z, const float* ec, const float* eu, const float* w, float* out, int b,
                              int D, float alpha, float sigma, float alpha_n, float c, float var_sqrt, int add_noise,
-                             unsigned long long seed, hipStream_t st) {
+                             unsigned long long seed, int pred, hipStream_t st) {
+  if (pred != 0 && pred != 1) return -1;
   long total = (long)b * D;
-  hipLaunchKernelGGL(sampler_step_k, dim3(ew_grid(total / 8 + 1)), dim3(256), 0, st, z, ec, eu, w, out, D, total,
+  hipLaunchKernelGGL(pred ? sampler_step_k<1> : sampler_step_k<0>, dim3(ew_grid(total / 8 + 1)), dim3(256), 0, st, z, ec, eu, w, out, D, total,
                      alpha, sigma, alpha_n, c, var_sqrt, add_noise, (uint64_t)seed);
   return (int)hipGetLastError();
 }
@@ -521,16 +586,18 @@ D3D_API int d3d_sampler_inputs(const float* xc, const float* z, int b, int HW, c
   return (int)hipGetLastError();
 }
 D3D_API int d3d_sampler_step2(float* z, const void* y, const float* w, int b, int HW, const float* prm,
-                              const void* sd, unsigned long long seed, long c0, hipStream_t st) {
+                              const void* sd, unsigned long long seed, long c0, int pred, hipStream_t st) {
+  if (pred != 0 && pred != 1) return -1;
   long total = (long)b * 3 * HW;
-  hipLaunchKernelGGL(sampler_step2_k, dim3(ew_grid(total)), dim3(256), 0, st, z, (const bf16*)y, w, b, HW, prm,
+  hipLaunchKernelGGL(pred ? sampler_step2_k<1> : sampler_step2_k<0>, dim3(ew_grid(total)), dim3(256), 0, st, z, (const bf16*)y, w, b, HW, prm,
                      (const uint64_t*)sd, (uint64_t)seed, c0);
   return (int)hipGetLastError();
 }
 D3D_API int d3d_sampler_solve(float* z, float* x0p, const void* y, const float* w, int b, int HW, const float* prm,
-                              const void* sd, unsigned long long seed, long c0, hipStream_t st) {
+                              const void* sd, unsigned long long seed, long c0, int pred, hipStream_t st) {
+  if (pred != 0 && pred != 1) return -1;
   long total = (long)b * HW;
-  hipLaunchKernelGGL(sampler_solve_k, dim3(ew_grid(total)), dim3(256), 0, st, z, x0p, (const bf16*)y, w, b, HW, prm,
+  hipLaunchKernelGGL(pred ? sampler_solve_k<1> : sampler_solve_k<0>, dim3(ew_grid(total)), dim3(256), 0, st, z, x0p, (const bf16*)y, w, b, HW, prm,
                      (const uint64_t*)sd, (uint64_t)seed, c0);
   return (int)hipGetLastError();
 }
@@ -540,26 +607,31 @@ D3D_API int d3d_randn_hash(float* out, long n, unsigned long long seed, long off
 }
 D3D_API int d3d_diffusion_fwd2(const float* img, int B, int HW, unsigned long long seed, const void* seed_dev,
                                long e0, float cond_prob, float a, float b0, float* eps, float* logsnr,
-                               unsigned char* keep, void* xz, hipStream_t st) {
+                               unsigned char* keep, void* xz, int pred, hipStream_t st) {
+  if (pred != 0 && pred != 1) return -1;
   long total = (long)B * HW;
-  hipLaunchKernelGGL(diffusion_fwd2_k, dim3(ew_grid(total)), dim3(256), 0, st, img, B, HW, (uint64_t)seed,
+  hipLaunchKernelGGL(pred ? diffusion_fwd2_k<1> : diffusion_fwd2_k<0>, dim3(ew_grid(total)), dim3(256), 0, st, img, B, HW, (uint64_t)seed,
                      (const uint64_t*)seed_dev, e0, cond_prob, a, b0, eps, logsnr, keep, (bf16*)xz);
   return (int)hipGetLastError();
 }
+// wmode: the WM of diff_loss_part_k / diff_loss_bwd_k (0 none, 1 min-SNR for an
+// eps target, 2 min-SNR for a v target); logsnr [B,2] is required unless 0.
 D3D_API int d3d_diff_loss(const void* y, const float* eps, int B, int HW, int CP, int mode, float* part, float* out,
-                          hipStream_t st) {
-  if (CP != 8) return -1;
-  hipLaunchKernelGGL(diff_loss_part_k, dim3(LOSS_BLOCKS), dim3(256), 0, st, (const bf16*)y, eps, B, HW, CP, mode,
+                          const float* logsnr, int wmode, float gamma, hipStream_t st) {
+  if (CP != 8 || wmode < 0 || wmode > 2 || (wmode != 0 && !logsnr)) return -1;
+  auto k = wmode == 0 ? diff_loss_part_k<0> : (wmode == 1 ? diff_loss_part_k<1> : diff_loss_part_k<2>);
+  hipLaunchKernelGGL(k, dim3(LOSS_BLOCKS), dim3(256), 0, st, (const bf16*)y, eps, B, HW, CP, mode, logsnr, gamma,
                      part);
   hipLaunchKernelGGL(diff_loss_final_k, dim3(1), dim3(256), 0, st, part, LOSS_BLOCKS, 1.f / (3.f * B * HW), out);
   return (int)hipGetLastError();
 }
 D3D_API int d3d_diff_loss_bwd(const void* y, const float* eps, const float* dloss, int B, int HW, int CP, int mode,
-                              void* dy, hipStream_t st) {
-  if (CP != 8) return -1;
+                              void* dy, const float* logsnr, int wmode, float gamma, hipStream_t st) {
+  if (CP != 8 || wmode < 0 || wmode > 2 || (wmode != 0 && !logsnr)) return -1;
   long total = (long)B * HW;
-  hipLaunchKernelGGL(diff_loss_bwd_k, dim3(ew_grid(total)), dim3(256), 0, st, (const bf16*)y, eps, dloss, B, HW, CP,
-                     mode, 1.f / (3.f * B * HW), (bf16*)dy);
+  auto k = wmode == 0 ? diff_loss_bwd_k<0> : (wmode == 1 ? diff_loss_bwd_k<1> : diff_loss_bwd_k<2>);
+  hipLaunchKernelGGL(k, dim3(ew_grid(total)), dim3(256), 0, st, (const bf16*)y, eps, dloss, B, HW, CP, mode,
+                     1.f / (3.f * B * HW), logsnr, gamma, (bf16*)dy);
   return (int)hipGetLastError();
 }
 

@@ -2700,12 +2700,24 @@ def adam_flat_dev(p, g, m, v, ema, hp, refresh=True):
 
 
 # ------------------------------------------- training input and loss ---
-def diffusion_inputs(img, seed, e0=0, cond_prob=0.1, logsnr_min=-20.0, logsnr_max=20.0, dtype=BF16):
+_PREDS = {"eps": 0, "v": 1}
+
+
+def _pred(prediction):
+    if prediction not in _PREDS:
+        raise ValueError(f"prediction {prediction!r}: expected one of {sorted(_PREDS)}")
+    return _PREDS[prediction]
+
+
+def diffusion_inputs(img, seed, e0=0, cond_prob=0.1, logsnr_min=-20.0, logsnr_max=20.0, dtype=BF16, *,
+                     prediction="eps"):
     """One launch (diffusion_fwd2_k): t, lambda, eps, z_t, CFG drop -> the
-    stem's NHWC bf16 input, eps, logsnr [B,2], keep mask.  Same numbers as
+    stem's NHWC bf16 input, the loss target (eps, or v = alpha eps - sigma
+    z_clean for ``prediction="v"``), logsnr [B,2], keep mask.  Same numbers as
     ``torch_impl.diffusion_inputs``; in a graph replay the per-step part of the
     seed is the device word of :func:`set_device_seed`."""
     assert dtype == BF16
+    pred = _pred(prediction)
     img = img.float().contiguous()
     B, _, C, H, W = img.shape
     assert C == 3, img.shape
@@ -2717,7 +2729,7 @@ def diffusion_inputs(img, seed, e0=0, cond_prob=0.1, logsnr_min=-20.0, logsnr_ma
     a, b = _t.schedule_ab(logsnr_min, logsnr_max)
     _chk(_lib.d3d_diffusion_fwd2(img.data_ptr(), B, H * W, int(seed) & 0xFFFFFFFFFFFFFFFF, _ptr(_SEED_DEV[0]), int(e0),
                                  float(cond_prob), float(a), float(b), eps.data_ptr(), lam.data_ptr(),
-                                 keep.data_ptr(), xz.data_ptr(), _st()), "diffusion_fwd2")
+                                 keep.data_ptr(), xz.data_ptr(), pred, _st()), "diffusion_fwd2")
     return xz, eps, lam, keep.view(torch.bool)
 
 
@@ -2726,36 +2738,49 @@ _LOSS_MODES = {"l2": 0, "l1": 1, "huber": 2}
 
 class _DiffLoss(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, y, eps, mode):
+    def forward(ctx, y, eps, mode, logsnr=None, wmode=0, gamma=5.0):
         B, H, W, CP = y.shape
         part = torch.empty(256, dtype=F32, device=y.device)
         out = torch.empty((), dtype=F32, device=y.device)
         _chk(_lib.d3d_diff_loss(y.data_ptr(), eps.data_ptr(), B, H * W, CP, mode, part.data_ptr(), out.data_ptr(),
-                                _st()), "diff_loss")
-        ctx.save_for_backward(y, eps)
-        ctx.mode = mode
+                                _ptr(logsnr), wmode, float(gamma), _st()), "diff_loss")
+        if logsnr is None:
+            ctx.save_for_backward(y, eps)
+        else:
+            ctx.save_for_backward(y, eps, logsnr)
+        ctx.mode, ctx.wmode, ctx.gamma = mode, wmode, float(gamma)
         return out
 
     @staticmethod
     def backward(ctx, dl):
-        y, eps = ctx.saved_tensors
+        y, eps, *rest = ctx.saved_tensors
+        logsnr = rest[0] if rest else None
         B, H, W, CP = y.shape
         dl = dl.float().contiguous()
         dy = torch.empty_like(y)
         _chk(_lib.d3d_diff_loss_bwd(y.data_ptr(), eps.data_ptr(), dl.data_ptr(), B, H * W, CP, ctx.mode,
-                                    dy.data_ptr(), _st()), "diff_loss_bwd")
-        return dy, None, None
+                                    dy.data_ptr(), _ptr(logsnr), ctx.wmode, ctx.gamma, _st()), "diff_loss_bwd")
+        return dy, None, None, None, None, None
 
 
-def diff_loss_nhwc(y, eps, loss_type="l2"):
-    """Epsilon loss read straight from the channel-padded NHWC head output
-    (two launches forward, one backward; deterministic partial sums)."""
+def diff_loss_nhwc(y, eps, loss_type="l2", *, logsnr=None, prediction="eps", loss_weight="none", gamma=5.0):
+    """Diffusion loss read straight from the channel-padded NHWC head output
+    against the target ``eps`` (eps or v) (two launches forward, one backward;
+    deterministic partial sums).  ``loss_weight="min_snr"``: the min-SNR-gamma
+    weight of ``logsnr[:, 1]`` per example, computed in the kernels."""
     if loss_type not in _LOSS_MODES:
         raise ValueError(f"loss_type {loss_type!r}: expected one of {sorted(_LOSS_MODES)}")
+    wmode = _t.loss_weight_mode(prediction, loss_weight, logsnr)
+    kw = dict(logsnr=logsnr, prediction=prediction, loss_weight=loss_weight, gamma=gamma)
     if y.shape[-1] != 8 or y.dtype != BF16:
         _fallback("diff_loss", f"head layout {tuple(y.shape)} {y.dtype}")
-        return _t.diff_loss_nhwc(y, eps, loss_type)
-    return _DiffLoss.apply(y.contiguous(), eps.float().contiguous(), _LOSS_MODES[loss_type])
+        return _t.diff_loss_nhwc(y, eps, loss_type, **kw)
+    if wmode == 0:
+        return _DiffLoss.apply(y.contiguous(), eps.float().contiguous(), _LOSS_MODES[loss_type])
+    B = y.shape[0]
+    assert logsnr.shape == (B, 2) and logsnr.device == y.device, (tuple(logsnr.shape), logsnr.device)
+    return _DiffLoss.apply(y.contiguous(), eps.float().contiguous(), _LOSS_MODES[loss_type],
+                           logsnr.detach().float().contiguous(), wmode, float(gamma))
 
 
 # ------------------------------------------------------------- sampler ---
@@ -2767,25 +2792,29 @@ def sampler_inputs(xc, z, prm, sd, seed, c0, xz, logsnr):
          "sampler_inputs")
 
 
-def sampler_step2(z, y, w, prm, sd, seed, c0):
+def sampler_step2(z, y, w, prm, sd, seed, c0, *, prediction="eps"):
+    """Ancestral CFG step on the bf16 head output ``y`` [2b,H,W,8] (eps, or v
+    with ``prediction="v"``); ``z`` fp32 [b,3,H,W] in place."""
     b = z.shape[0]
     HW = z.shape[-1] * z.shape[-2]
     assert y.shape[-1] == 8 and y.shape[0] == 2 * b and z.is_contiguous()
     _chk(_lib.d3d_sampler_step2(z.data_ptr(), y.data_ptr(), w.data_ptr(), b, HW, prm.data_ptr(), _ptr(sd),
-                                int(seed) & 0xFFFFFFFFFFFFFFFF, int(c0), _st()), "sampler_step2")
+                                int(seed) & 0xFFFFFFFFFFFFFFFF, int(c0), _pred(prediction), _st()), "sampler_step2")
 
 
-def sampler_solve(z, x0_prev, y, w, prm, sd, seed, c0):
+def sampler_solve(z, x0_prev, y, w, prm, sd, seed, c0, *, prediction="eps"):
     """Few-step solver update (``diffusion.solver_step`` on the device): ``z``
     and ``x0_prev`` fp32 [b,3,H,W] in place, ``y`` the bf16 [2b,H,W,8] head
-    output, ``prm`` the ``diffusion.solver_row`` of the step."""
+    output (eps, or v with ``prediction="v"``), ``prm`` the
+    ``diffusion.solver_row`` of the step."""
     b = z.shape[0]
     HW = z.shape[-1] * z.shape[-2]
     assert y.shape[-1] == 8 and y.shape[0] == 2 * b and y.dtype == BF16 and y.is_contiguous()
     assert z.dtype == F32 and z.is_contiguous() and x0_prev.dtype == F32 and x0_prev.is_contiguous()
     assert x0_prev.shape == z.shape and y.numel() == 2 * b * HW * 8 and w.numel() == b and prm.numel() >= 8
     _chk(_lib.d3d_sampler_solve(z.data_ptr(), x0_prev.data_ptr(), y.data_ptr(), w.data_ptr(), b, HW, prm.data_ptr(),
-                                _ptr(sd), int(seed) & 0xFFFFFFFFFFFFFFFF, int(c0), _st()), "sampler_solve")
+                                _ptr(sd), int(seed) & 0xFFFFFFFFFFFFFFFF, int(c0), _pred(prediction), _st()),
+         "sampler_solve")
 
 
 def randn_hash(shape, seed, off, device):
@@ -2795,13 +2824,13 @@ def randn_hash(shape, seed, off, device):
     return out
 
 
-def sampler_step(z, eps_c, eps_u, w, alpha, sigma, alpha_n, c, var_sqrt, add_noise, seed):
+def sampler_step(z, eps_c, eps_u, w, alpha, sigma, alpha_n, c, var_sqrt, add_noise, seed, *, prediction="eps"):
     b = z.shape[0]
     D = z[0].numel()
     out = torch.empty_like(z)
     _chk(_lib.d3d_sampler_step(z.data_ptr(), eps_c.contiguous().data_ptr(), eps_u.contiguous().data_ptr(),
                                w.float().contiguous().data_ptr(), out.data_ptr(), b, D, alpha, sigma, alpha_n, c,
-                               var_sqrt, int(add_noise), int(seed), _st()), "sampler_step")
+                               var_sqrt, int(add_noise), int(seed), _pred(prediction), _st()), "sampler_step")
     return out
 
 

@@ -306,12 +306,16 @@ def schedule_ab(logsnr_min: float, logsnr_max: float):
 
 
 def diffusion_inputs(img: torch.Tensor, seed: int, e0: int = 0, cond_prob: float = 0.1,
-                     logsnr_min: float = -20.0, logsnr_max: float = 20.0, dtype=torch.float32):
+                     logsnr_min: float = -20.0, logsnr_max: float = 20.0, dtype=torch.float32,
+                     prediction: str = "eps"):
     """The training-input draw of `train.py:80-100` for examples
     ``e0 .. e0+B-1`` of a step whose RNG seed is ``seed`` (same numbers as
     ``diffusion_fwd2_k``).  img [B,2,3,H,W] -> (xz [2B,H,W,8] NHWC stem input
-    (frame 0 = CFG-dropped x, frame 1 = z_t; channels 3..7 zero), eps
-    [B,3,H,W] fp32, logsnr [B,2], keep [B] bool)."""
+    (frame 0 = CFG-dropped x, frame 1 = z_t; channels 3..7 zero), the loss
+    target [B,3,H,W] fp32 (``prediction="eps"``: eps; ``"v"``: alpha eps -
+    sigma z_clean), logsnr [B,2], keep [B] bool)."""
+    if prediction not in ("eps", "v"):
+        raise ValueError(f"prediction {prediction!r}: expected 'eps' or 'v'")
     B, _, C, H, W = img.shape
     HW = H * W
     dev = img.device
@@ -339,20 +343,44 @@ def diffusion_inputs(img: torch.Tensor, seed: int, e0: int = 0, cond_prob: float
     xz = torch.zeros(B, 2, H, W, 8, dtype=dtype, device=dev)
     xz[:, 0, ..., :3] = xc.permute(0, 2, 3, 1).to(dtype)
     xz[:, 1, ..., :3] = zt.permute(0, 2, 3, 1).to(dtype)
-    return xz.reshape(2 * B, H, W, 8), eps, torch.stack([lam0, lam], 1), keep
+    target = eps if prediction == "eps" else alpha * eps - sigma * z
+    return xz.reshape(2 * B, H, W, 8), target, torch.stack([lam0, lam], 1), keep
 
 
-def diff_loss_nhwc(y: torch.Tensor, eps: torch.Tensor, loss_type: str = "l2") -> torch.Tensor:
-    """Epsilon loss (`train.py:102-112`) on the NHWC head output y [B,H,W,>=3]
-    (only the first 3 channels are the prediction) against eps [B,3,H,W]."""
+def loss_weight_mode(prediction: str, loss_weight: str, logsnr) -> int:
+    """The loss kernels' weight switch: 0 none, 1 min-SNR for an eps target, 2
+    min-SNR for a v target (validates the three arguments)."""
+    if prediction not in ("eps", "v"):
+        raise ValueError(f"prediction {prediction!r}: expected 'eps' or 'v'")
+    if loss_weight not in ("none", "min_snr"):
+        raise ValueError(f"loss_weight {loss_weight!r}: expected 'none' or 'min_snr'")
+    if loss_weight == "none":
+        return 0
+    if logsnr is None:
+        raise ValueError(f"loss_weight={loss_weight!r} needs the batch's logsnr [B,2]")
+    return 1 if prediction == "eps" else 2
+
+
+def diff_loss_nhwc(y: torch.Tensor, eps: torch.Tensor, loss_type: str = "l2", *, logsnr=None,
+                   prediction: str = "eps", loss_weight: str = "none", gamma: float = 5.0) -> torch.Tensor:
+    """Diffusion loss (`train.py:102-112`) on the NHWC head output y [B,H,W,>=3]
+    (only the first 3 channels are the prediction) against the target ``eps``
+    [B,3,H,W] (eps or v).  ``loss_weight="min_snr"``: each example's mean is
+    weighted by min-SNR-gamma of ``logsnr[:, 1]`` (``diffusion.min_snr_weight``;
+    ``logsnr`` the [B,2] tensor of :func:`diffusion_inputs`), not normalised."""
+    wm = loss_weight_mode(prediction, loss_weight, logsnr)
     yh = y[..., :3].permute(0, 3, 1, 2).float()
-    if loss_type == "l2":
-        return torch.mean((eps.float() - yh) ** 2)
-    if loss_type == "l1":
-        return torch.mean((eps.float() - yh).abs())
-    if loss_type == "huber":
-        return F.smooth_l1_loss(yh, eps.float())
-    raise NotImplementedError(loss_type)
+    if wm == 0:
+        if loss_type == "l2":
+            return torch.mean((eps.float() - yh) ** 2)
+        if loss_type == "l1":
+            return torch.mean((eps.float() - yh).abs())
+        if loss_type == "huber":
+            return F.smooth_l1_loss(yh, eps.float())
+        raise NotImplementedError(loss_type)
+    from ..diffusion import diffusion_loss
+    return diffusion_loss(eps, yh, loss_type, logsnr=logsnr[:, 1], prediction=prediction, loss_weight=loss_weight,
+                          gamma=gamma)
 
 
 # ----------------------------------------------------------- image metrics ---

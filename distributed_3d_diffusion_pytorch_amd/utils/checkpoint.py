@@ -74,6 +74,15 @@ def load_checkpoint(path: str, map_location="cpu") -> Dict[str, Any]:
     return torch.load(path, map_location=map_location, weights_only=True)
 
 
+def checkpoint_prediction(ck: Dict[str, Any]) -> str:
+    """What the checkpoint's model outputs: its ``config.diffusion.prediction``;
+    a file without a config (a reference checkpoint) or from before the field
+    existed is an eps model."""
+    cfg = ck.get("config") if isinstance(ck, dict) else None
+    diff = cfg.get("diffusion") if isinstance(cfg, dict) else None
+    return str(diff.get("prediction", "eps")) if isinstance(diff, dict) else "eps"
+
+
 def load_model_weights(model: torch.nn.Module, sd: Dict[str, torch.Tensor], strict: bool = True):
     """Load a (possibly ``module.``-prefixed) state dict IN PLACE, preserving
     the flat-buffer views the parameters live in."""

@@ -41,6 +41,8 @@ def parse(argv=None):
                     help="update rule: the 256-step ancestral chain, DDIM or DPM-Solver++(2M) for few steps")
     ap.add_argument("--eta", type=float, default=0.0, help="DDIM noise level in [0, 1] (1 = ancestral variance)")
     ap.add_argument("--spacing", default="t", choices=["t", "logsnr"], help="steps uniform in t or in logSNR")
+    ap.add_argument("--prediction", default="auto", choices=["auto", "eps", "v"],
+                    help="what the model outputs; auto: the checkpoint's config.diffusion.prediction (eps without one)")
     ap.add_argument("--imgsize", type=int, default=64)
     ap.add_argument("--batch", type=int, default=64, help="objects per sampler batch")
     ap.add_argument("--autoregressive", action="store_true", help="generated views join the record")
@@ -54,9 +56,12 @@ def parse(argv=None):
     return ap.parse_args(argv)
 
 
-def val_loss(model, cfg, args, dev) -> float:
-    """The training loss on the first ``val_batches * val_batch_size`` pairs of
-    the split, with the fixed validation draw of ``Trainer.validation_loss``."""
+def val_loss(model, cfg, args, dev, prediction: str) -> float:
+    """The training loss (the checkpoint's configured, weighted objective, for
+    the target of ``prediction``) on the first ``val_batches * val_batch_size``
+    pairs of the split, with the fixed validation draw of
+    ``Trainer.validation_loss``."""
+    import dataclasses
     from distributed_3d_diffusion_pytorch_amd.config import DiffusionConfig
     from distributed_3d_diffusion_pytorch_amd.data import SRNDataset, collate
     from distributed_3d_diffusion_pytorch_amd.engine import heldout_loss
@@ -66,7 +71,7 @@ def val_loss(model, cfg, args, dev) -> float:
         raise ValueError(f"no instances in the {args.split} split of {args.data}")
     batches = (tuple(t.to(dev) for t in collate([ds[i] for i in range(s, min(s + args.val_batch_size, n))]))
                for s in range(0, n, args.val_batch_size))
-    dc = cfg.diffusion if cfg is not None else DiffusionConfig()
+    dc = dataclasses.replace(cfg.diffusion if cfg is not None else DiffusionConfig(), prediction=prediction)
     return float(heldout_loss(model, batches, args.seed, dc, model.compute_dtype))
 
 
@@ -74,7 +79,7 @@ def run(args) -> dict:
     import torch
     from distributed_3d_diffusion_pytorch_amd import ops
     from distributed_3d_diffusion_pytorch_amd.engine import evaluate_objects, load_objects, summarize
-    from distributed_3d_diffusion_pytorch_amd.engine.evaluate import load_model
+    from distributed_3d_diffusion_pytorch_amd.engine.evaluate import load_model, resolve_prediction
 
     if args.backend != "auto":
         ops.set_backend(args.backend)
@@ -83,6 +88,8 @@ def run(args) -> dict:
     views = [int(v) for v in args.views.split(",")]
     w = [float(x) for x in args.w.split(",")]
     model, cfg = load_model(args.model, args.imgsize, dev, args.ema)
+    prediction = resolve_prediction(args.prediction, cfg)
+    print(f"[evaluate] prediction {prediction}", flush=True)
     objects = load_objects(args.data, args.index, args.split, args.instances, args.imgsize,
                            sorted({args.input_view, *views}))
     if not objects:
@@ -103,13 +110,13 @@ def run(args) -> dict:
     rows, _ = evaluate_objects(model, objects, args.input_view, views, w, args.timesteps, args.batch,
                                args.autoregressive, args.seed, dev,
                                on_view=write_pngs if args.save_png else None, solver=args.sampler, eta=args.eta,
-                               spacing=args.spacing)
+                               spacing=args.spacing, prediction=prediction)
     if dev.type == "cuda":
         torch.cuda.synchronize(dev)
     t2 = time.time()
-    result = {"args": vars(args), "per_image": rows, **summarize(rows)}
+    result = {"args": vars(args), "prediction": prediction, "per_image": rows, **summarize(rows)}
     if args.val_batches > 0:
-        result["val_loss"] = val_loss(model, cfg, args, dev)
+        result["val_loss"] = val_loss(model, cfg, args, dev, prediction)
     result["sample_seconds"] = t2 - t1
     result["wall_seconds"] = time.time() - t0
     tmp = os.path.join(args.out, "metrics.json.tmp")

@@ -42,6 +42,8 @@ def parse(argv=None):
                     help="update rule: the ancestral chain, DDIM or DPM-Solver++(2M) for few steps")
     ap.add_argument("--eta", type=float, default=0.0, help="DDIM noise level in [0, 1] (1 = ancestral variance)")
     ap.add_argument("--spacing", default="t", choices=["t", "logsnr"], help="steps uniform in t or in logSNR")
+    ap.add_argument("--prediction", default="auto", choices=["auto", "eps", "v"],
+                    help="what the model outputs; auto: the checkpoint's config.diffusion.prediction (eps without one)")
     ap.add_argument("--w", default="0,1,2,3,4,5,6,7", help="guidance weights, one chain each")
     ap.add_argument("--max_views", type=int, default=0, help="generate at most this many views (0 = all)")
     ap.add_argument("--ema", action="store_true", help="use EMA weights when the checkpoint has them")
@@ -81,7 +83,7 @@ def run(args) -> None:
     import torch.distributed as dist
     from distributed_3d_diffusion_pytorch_amd import ops
     from distributed_3d_diffusion_pytorch_amd.engine import DiffusionSampler, RecordEntry, shard_range
-    from distributed_3d_diffusion_pytorch_amd.engine.evaluate import load_model
+    from distributed_3d_diffusion_pytorch_amd.engine.evaluate import load_model, resolve_prediction
     from distributed_3d_diffusion_pytorch_amd.parallel import init_distributed, cleanup
 
     ctx = init_distributed("auto")
@@ -89,7 +91,10 @@ def run(args) -> None:
     if args.backend != "auto":
         ops.set_backend(args.backend)
     imgs, Rs, Ts, K = load_instance(args.target, args.imgsize)
-    model, _ = load_model(args.model, args.imgsize, dev, args.ema)
+    model, cfg = load_model(args.model, args.imgsize, dev, args.ema)
+    prediction = resolve_prediction(args.prediction, cfg)
+    if ctx.is_main:
+        print(f"[sampling] prediction {prediction}", flush=True)
 
     w_all = torch.tensor([float(x) for x in args.w.split(",")])
     s, e = shard_range(len(w_all), ctx.rank, ctx.world)
@@ -99,7 +104,7 @@ def run(args) -> None:
     # noise is keyed by the GLOBAL chain index (chain_offset), so the gathered
     # result does not depend on the number of ranks
     sampler = DiffusionSampler(model, args.timesteps, args.ref_quirk, seed=args.seed, device=dev, chain_offset=s,
-                               solver=args.sampler, eta=args.eta, spacing=args.spacing)
+                               solver=args.sampler, eta=args.eta, spacing=args.spacing, prediction=prediction)
     t = lambda a: torch.tensor(a, dtype=torch.float32, device=dev)  # noqa: E731
     record = [RecordEntry(t(imgs[0])[None].expand(b, -1, -1, -1).contiguous(), t(Rs[0]), t(Ts[0]))]
     if ctx.is_main:
@@ -139,7 +144,7 @@ def run(args) -> None:
     if args.metrics and ctx.is_main:
         with open(os.path.join(args.out, "metrics.json"), "w") as f:
             json.dump({"target": args.target, "sampler": args.sampler, "eta": args.eta, "spacing": args.spacing,
-                       "per_image": rows}, f, indent=1, allow_nan=False)
+                       "prediction": prediction, "per_image": rows}, f, indent=1, allow_nan=False)
     cleanup()
 
 

@@ -72,7 +72,8 @@ def run(args) -> None:
         cfg.dtype = "fp32"
     if ctx.is_main:
         print(f"[train] world={ctx.world} device={ctx.device} global_batch={cfg.global_batch} "
-              f"img={cfg.model.H} data={'synthetic' if cfg.data.synthetic else cfg.data.path}", flush=True)
+              f"img={cfg.model.H} data={'synthetic' if cfg.data.synthetic else cfg.data.path} "
+              f"prediction={cfg.diffusion.prediction} loss_weight={cfg.diffusion.loss_weight}", flush=True)
     try:
         trainer = Trainer(cfg, ctx)
         trainer.fit()
