@@ -113,6 +113,24 @@ def diffusion_loss(eps: torch.Tensor, eps_hat: torch.Tensor, loss_type: str = "l
     return torch.mean(wgt.view((-1,) + (1,) * (el.dim() - 1)) * el)
 
 
+def loss_bins_report(table, logsnr_min: float = -20.0, logsnr_max: float = 20.0) -> dict:
+    """The noise-level table of ``ops.loss_bins_add`` ([NB,5]: count, sum of
+    the loss, of the weighted loss, of the squared error in eps units and in
+    x0 units; bins uniform in t) as a JSON-ready dict: ``t_edges`` and
+    ``logsnr_edges`` (NB + 1 values), ``count`` and the per-bin means ``loss``,
+    ``weighted``, ``mse_eps``, ``mse_x0`` (None for an empty bin).  Only
+    ``mse_eps`` and ``mse_x0`` compare across objectives."""
+    rows = table.detach().double().cpu().tolist() if isinstance(table, torch.Tensor) else [list(r) for r in table]
+    nb = len(rows)
+    a, b = _ab(logsnr_min, logsnr_max)
+    t_edges = [j / nb for j in range(nb + 1)]
+    out = {"t_edges": t_edges, "logsnr_edges": [-2.0 * math.log(math.tan(a * t + b)) for t in t_edges],
+           "count": [int(round(r[0])) for r in rows]}
+    for col, name in enumerate(("loss", "weighted", "mse_eps", "mse_x0"), start=1):
+        out[name] = [r[col] / r[0] if r[0] > 0 else None for r in rows]
+    return out
+
+
 SPACINGS = ("t", "logsnr")
 SOLVERS = ("ancestral", "ddim", "dpmpp2m")
 

@@ -34,14 +34,16 @@ def validation_seed(seed: int, i: int) -> int:
 
 
 @torch.no_grad()
-def heldout_loss(model, batches: Iterable, seed: int, diffusion_cfg, dtype) -> torch.Tensor:
+def heldout_loss(model, batches: Iterable, seed: int, diffusion_cfg, dtype, bins=None) -> torch.Tensor:
     """Mean training loss (``ops.diffusion_inputs`` -> forward ->
     ``ops.diff_loss_nhwc``) of ``model`` in eval mode over ``batches`` of
     (img [B,2,3,H,W], R, T, K) on the model's device -- the configured
     objective: the target of ``diffusion_cfg.prediction`` under its
     ``loss_weight`` -- batch i drawn with
-    ``validation_seed(seed, i)``.  Returns a device scalar; the model's
-    train / eval mode is restored, nothing else is touched."""
+    ``validation_seed(seed, i)``.  ``bins``: an fp64 [NB,5] table on the
+    model's device that every batch is added to (``ops.diff_loss_rows`` ->
+    ``ops.loss_bins_add``: the loss by noise level).  Returns a device scalar;
+    the model's train / eval mode is restored, nothing else is touched."""
     dc = diffusion_cfg
     was_training = model.training
     model.eval()
@@ -54,6 +56,10 @@ def heldout_loss(model, batches: Iterable, seed: int, diffusion_cfg, dtype) -> t
             y = model({"xz": xz, "logsnr": logsnr, "R": R, "t": T, "K": K}, cond_mask=keep, head_nhwc=True)
             loss = ops.diff_loss_nhwc(y, eps, dc.loss_type, logsnr=logsnr, prediction=dc.prediction,
                                       loss_weight=dc.loss_weight, gamma=dc.min_snr_gamma).detach().float()
+            if bins is not None:
+                ops.loss_bins_add(bins, ops.diff_loss_rows(y, eps, dc.loss_type), logsnr, prediction=dc.prediction,
+                                  loss_weight=dc.loss_weight, gamma=dc.min_snr_gamma, logsnr_min=dc.logsnr_min,
+                                  logsnr_max=dc.logsnr_max)
             total = loss if total is None else total + loss
             n += 1
     finally:

@@ -355,7 +355,7 @@ class Trainer:
 
     # ------------------------------------------------------------------
     @torch.no_grad()
-    def validation_loss(self, batches) -> float:
+    def validation_loss(self, batches, bins: int = 0):
         """Mean training loss (``ops.diffusion_inputs`` -> forward ->
         ``ops.diff_loss_nhwc``) over ``batches`` of (img, R, T, K), in eval
         mode.  The draw of batch i is seeded by (cfg.seed, a validation
@@ -363,15 +363,24 @@ class Trainer:
         scores the same (t, eps, CFG-drop) draw and the values of different
         steps are comparable.  Averaged over ranks.  Reads the parameters
         only: the optimizer, the step counter, the RNG states, the dropout
-        seed word and the gradient buffers stay as they are."""
+        seed word and the gradient buffers stay as they are.  ``bins`` > 0:
+        also return the pass's loss by noise level in that many bins, summed
+        over the ranks (``diffusion.loss_bins_report``): ``(mean, report)``."""
         from .evaluate import heldout_loss
         self.sync()                         # the graph step may still hold the last update
+        table = torch.zeros(bins, 5, dtype=torch.float64, device=self.device) if bins > 0 else None
         mean = heldout_loss(self.model, (self._to_dev(b) for b in batches), self.cfg.seed, self.cfg.diffusion,
-                            self.dtype)
+                            self.dtype, bins=table)
         if self.ctx.world > 1:
             import torch.distributed as dist
             dist.all_reduce(mean)
             mean = mean / self.ctx.world
+            if table is not None:
+                dist.all_reduce(table)
+        if table is not None:
+            from ..diffusion import loss_bins_report
+            dc = self.cfg.diffusion
+            return float(mean), loss_bins_report(table, dc.logsnr_min, dc.logsnr_max)
         return float(mean)
 
     def make_val_data(self) -> list:

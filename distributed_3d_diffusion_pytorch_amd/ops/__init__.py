@@ -158,6 +158,28 @@ def diff_loss_nhwc(y, target, loss_type: str = "l2", *, logsnr=None, prediction:
     return _t.diff_loss_nhwc(y, target, loss_type, **kw)
 
 
+def diff_loss_rows(y, target, loss_type: str = "l2"):
+    """Per-example loss rows [B,2] fp32 (no autograd): column 0 the example's
+    mean of l(y - target), column 1 its mean of (y - target)^2, over the 3 H W
+    valid elements of the NHWC head output."""
+    if use_hip(y):
+        return _h().diff_loss_rows(y, target, loss_type)
+    return _t.diff_loss_rows(y, target, loss_type)
+
+
+def loss_bins_add(table, rows, logsnr, *, prediction: str = "eps", loss_weight: str = "none", gamma: float = 5.0,
+                  logsnr_min: float = -20.0, logsnr_max: float = 20.0):
+    """Adds a batch to the noise-level table, in place: ``table`` fp64 [NB,5],
+    bins uniform in t, columns (count, sum row0, sum w row0, sum f_eps row1,
+    sum f_x row1) with ``rows`` of :func:`diff_loss_rows` and ``logsnr`` the
+    [B,2] tensor of :func:`diffusion_inputs` (see torch_impl.loss_bins_add)."""
+    kw = dict(prediction=prediction, loss_weight=loss_weight, gamma=gamma, logsnr_min=logsnr_min,
+              logsnr_max=logsnr_max)
+    if table.is_cuda and use_hip(table, any_dtype=True):
+        return _h().loss_bins_add(table, rows.float().contiguous(), logsnr.float().contiguous(), **kw)
+    return _t.loss_bins_add(table, rows, logsnr, **kw)
+
+
 def avgpool2(x):
     if use_hip(x):
         return _h().avgpool2(x)
@@ -220,7 +242,7 @@ posenc_ddpm = _t.posenc_ddpm
 camera_rays = _t.camera_rays
 posenc_nerf = _t.posenc_nerf
 
-__all__ = ["diffusion_inputs", "diff_loss_nhwc", "group_norm", "gn_film", "conv3x3", "linear", "film_batch", "cat_gn_silu_dense", "cond_conv", "ray_posenc_dir",
+__all__ = ["diffusion_inputs", "diff_loss_nhwc", "diff_loss_rows", "loss_bins_add", "group_norm", "gn_film", "conv3x3", "linear", "film_batch", "cat_gn_silu_dense", "cond_conv", "ray_posenc_dir",
            "ray_origin_pe", "ray_conditioning", "attention", "avgpool2", "upsample2",
            "silu", "logsnr_mlp", "ray_posenc", "image_metrics", "psnr", "posenc_ddpm", "camera_rays", "posenc_nerf", "set_backend",
            "use_hip", "load_library", "library_error", "lib_path"]

@@ -117,6 +117,10 @@ SIGNATURES = {
     "d3d_wgrad_group_engine": [P],
     "d3d_wgrad_group": [P, I, P, L, P],
     "d3d_wgrad_group_plan": [P, I, IP, IP, C.POINTER(C.c_long)],
+    # loss_stats.hip
+    "d3d_loss_rows_parts": [I],
+    "d3d_diff_loss_rows": [P, P, I, I, I, I, P, P, P],
+    "d3d_loss_bins": [P, I, P, P, I, I, I, C.c_double, C.c_double, C.c_double, P],
     # metrics.hip (taps: 11 host doubles)
     "d3d_image_metrics": [P, P, I, I, I, I, I, C.POINTER(C.c_double), P, P, P],
 }

@@ -2783,6 +2783,43 @@ def diff_loss_nhwc(y, eps, loss_type="l2", *, logsnr=None, prediction="eps", los
                            logsnr.detach().float().contiguous(), wmode, float(gamma))
 
 
+# ------------------------------------------------ loss by noise level ---
+def diff_loss_rows(y, target, loss_type="l2"):
+    """Per-example (mean l(y - target), mean (y - target)^2) [B,2] fp32 of the
+    padded NHWC bf16 head output (csrc/loss_stats.hip: a grid of (part,
+    example) blocks and a fixed-order sum of the parts; no autograd)."""
+    if loss_type not in _LOSS_MODES:
+        raise ValueError(f"loss_type {loss_type!r}: expected one of {sorted(_LOSS_MODES)}")
+    if y.dim() != 4 or y.shape[-1] != 8 or y.dtype != BF16:
+        raise ValueError(f"diff_loss_rows takes the padded bf16 head output [B,H,W,8], got {tuple(y.shape)} {y.dtype}")
+    B, H, W, CP = y.shape
+    y = y.detach().contiguous()
+    target = target.detach().float().contiguous()
+    assert target.shape == (B, 3, H, W) and target.device == y.device, (tuple(target.shape), target.device)
+    part = torch.empty(B, int(_lib.d3d_loss_rows_parts(H * W)), 2, dtype=F32, device=y.device)
+    rows = torch.empty(B, 2, dtype=F32, device=y.device)
+    _chk(_lib.d3d_diff_loss_rows(y.data_ptr(), target.data_ptr(), B, H * W, CP, _LOSS_MODES[loss_type],
+                                 part.data_ptr(), rows.data_ptr(), _st()), "diff_loss_rows")
+    return rows
+
+
+def loss_bins_add(table, rows, logsnr, *, prediction="eps", loss_weight="none", gamma=5.0, logsnr_min=-20.0,
+                  logsnr_max=20.0):
+    """table [NB,5] fp64 += the batch's per-bin sums (loss_bins_k: one block,
+    example order per bin, fp64 on the device); same numbers as
+    ``torch_impl.loss_bins_add``.  In place; graph-capturable."""
+    if table.dtype != torch.float64 or table.dim() != 2 or table.shape[1] != 5 or not table.is_contiguous():
+        raise ValueError(f"table: expected contiguous fp64 [NB,5], got {table.dtype} {tuple(table.shape)}")
+    wmode = _t.loss_weight_mode(prediction, loss_weight, logsnr)
+    B = rows.shape[0]
+    assert rows.shape == (B, 2) and rows.dtype == F32 and rows.is_contiguous() and rows.device == table.device
+    assert logsnr.shape == (B, 2) and logsnr.dtype == F32 and logsnr.is_contiguous() and logsnr.device == table.device
+    a, b = _t.schedule_ab(logsnr_min, logsnr_max)
+    _chk(_lib.d3d_loss_bins(table.data_ptr(), table.shape[0], rows.data_ptr(), logsnr.data_ptr(), B, _pred(prediction),
+                            wmode, float(gamma), float(a), float(b), _st()), "loss_bins")
+    return table
+
+
 # ------------------------------------------------------------- sampler ---
 def sampler_inputs(xc, z, prm, sd, seed, c0, xz, logsnr):
     b = z.shape[0]

@@ -383,6 +383,67 @@ def diff_loss_nhwc(y: torch.Tensor, eps: torch.Tensor, loss_type: str = "l2", *,
                           gamma=gamma)
 
 
+# ------------------------------------------------- loss by noise level ---
+def _element_loss(d: torch.Tensor, loss_type: str) -> torch.Tensor:
+    if loss_type == "l2":
+        return d * d
+    if loss_type == "l1":
+        return d.abs()
+    if loss_type == "huber":
+        ad = d.abs()
+        return torch.where(ad < 1.0, 0.5 * d * d, ad - 0.5)
+    raise ValueError(f"loss_type {loss_type!r}: expected 'l2', 'l1' or 'huber'")
+
+
+def diff_loss_rows(y: torch.Tensor, target: torch.Tensor, loss_type: str = "l2") -> torch.Tensor:
+    """Per-example loss rows [B,2] fp32 of the NHWC head output y [B,H,W,>=3]
+    against ``target`` [B,3,H,W]: column 0 the example's mean of l(y - target)
+    (l the ``loss_type``), column 1 its mean of (y - target)^2, both over the
+    3 H W valid elements.  No autograd."""
+    d = y.detach()[..., :3].permute(0, 3, 1, 2).float() - target.detach().float()
+    el = _element_loss(d, loss_type)
+    return torch.stack([el.flatten(1).mean(1), (d * d).flatten(1).mean(1)], 1)
+
+
+def loss_bin_terms(lam: torch.Tensor, prediction: str, loss_weight: str, gamma: float, nbins: int,
+                   logsnr_min: float, logsnr_max: float):
+    """(bin [B] int64, w, f_eps, f_x [B] fp64) of the examples' fp32 ``lam``:
+    bins uniform in t through the schedule's inverse tau(lambda) = (atan(exp(
+    -lambda / 2)) - b) / a; w the configured loss weight; f_eps / f_x the
+    factors that turn the target's squared error into eps / x0 units."""
+    wm = loss_weight_mode(prediction, loss_weight, lam)
+    a, b = schedule_ab(logsnr_min, logsnr_max)
+    lam = lam.detach().double()
+    tau = (torch.atan(torch.exp(-0.5 * lam)) - b) / a
+    bins = torch.floor(tau * nbins).clamp(0, nbins - 1).to(torch.int64)
+    sp, sn = torch.sigmoid(lam), torch.sigmoid(-lam)
+    if wm == 0:
+        w = torch.ones_like(lam)
+    elif wm == 1:
+        w = torch.clamp(gamma * torch.exp(-lam), max=1.0)
+    else:
+        w = torch.minimum(sp, gamma * sn)
+    if prediction == "eps":
+        return bins, w, torch.ones_like(lam), torch.exp(-lam)
+    return bins, w, sp, sn
+
+
+def loss_bins_add(table: torch.Tensor, rows: torch.Tensor, logsnr: torch.Tensor, *, prediction: str = "eps",
+                  loss_weight: str = "none", gamma: float = 5.0, logsnr_min: float = -20.0,
+                  logsnr_max: float = 20.0) -> torch.Tensor:
+    """table [NB,5] fp64 += per bin of logsnr[:, 1]: (count, sum row0, sum w
+    row0, sum f_eps row1, sum f_x row1) over the batch's ``rows`` [B,2]
+    (:func:`diff_loss_rows`); see :func:`loss_bin_terms`.  In place."""
+    if table.dtype != torch.float64 or table.dim() != 2 or table.shape[1] != 5:
+        raise ValueError(f"table: expected fp64 [NB,5], got {table.dtype} {tuple(table.shape)}")
+    bins, w, fe, fx = loss_bin_terms(logsnr[:, 1], prediction, loss_weight, gamma, table.shape[0], logsnr_min,
+                                     logsnr_max)
+    r0, r1 = rows[:, 0].detach().double(), rows[:, 1].detach().double()
+    vals = torch.stack([torch.ones_like(r0), r0, w * r0, fe * r1, fx * r1], 1)
+    table.index_add_(0, bins, vals)          # (CPU: example order)
+    return table
+
+
 # ----------------------------------------------------------- image metrics ---
 SSIM_TAPS, SSIM_SIGMA = 11, 1.5
 SSIM_C1, SSIM_C2 = 0.01 ** 2, 0.03 ** 2

@@ -48,6 +48,8 @@ def parse(argv=None):
     ap.add_argument("--autoregressive", action="store_true", help="generated views join the record")
     ap.add_argument("--val_batches", type=int, default=0, help="also score the training loss on this many batches")
     ap.add_argument("--val_batch_size", type=int, default=16)
+    ap.add_argument("--loss_bins", type=int, default=0,
+                    help="with --val_batches: also write the loss by noise level in this many bins (val_loss_bins)")
     ap.add_argument("--ema", action="store_true", help="use EMA weights when the checkpoint has them")
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--out", default="evaluation")
@@ -56,13 +58,16 @@ def parse(argv=None):
     return ap.parse_args(argv)
 
 
-def val_loss(model, cfg, args, dev, prediction: str) -> float:
+def val_loss(model, cfg, args, dev, prediction: str):
     """The training loss (the checkpoint's configured, weighted objective, for
     the target of ``prediction``) on the first ``val_batches * val_batch_size``
     pairs of the split, with the fixed validation draw of
-    ``Trainer.validation_loss``."""
+    ``Trainer.validation_loss``.  Returns ``(loss, report)``: ``report`` the
+    loss by noise level in ``--loss_bins`` bins (None without them)."""
     import dataclasses
+    import torch
     from distributed_3d_diffusion_pytorch_amd.config import DiffusionConfig
+    from distributed_3d_diffusion_pytorch_amd.diffusion import loss_bins_report
     from distributed_3d_diffusion_pytorch_amd.data import SRNDataset, collate
     from distributed_3d_diffusion_pytorch_amd.engine import heldout_loss
     ds = SRNDataset(args.split, args.data, args.index, args.imgsize, seed=args.seed)
@@ -72,7 +77,9 @@ def val_loss(model, cfg, args, dev, prediction: str) -> float:
     batches = (tuple(t.to(dev) for t in collate([ds[i] for i in range(s, min(s + args.val_batch_size, n))]))
                for s in range(0, n, args.val_batch_size))
     dc = dataclasses.replace(cfg.diffusion if cfg is not None else DiffusionConfig(), prediction=prediction)
-    return float(heldout_loss(model, batches, args.seed, dc, model.compute_dtype))
+    table = torch.zeros(args.loss_bins, 5, dtype=torch.float64, device=dev) if args.loss_bins > 0 else None
+    loss = float(heldout_loss(model, batches, args.seed, dc, model.compute_dtype, bins=table))
+    return loss, (loss_bins_report(table, dc.logsnr_min, dc.logsnr_max) if table is not None else None)
 
 
 def run(args) -> dict:
@@ -116,7 +123,9 @@ def run(args) -> dict:
     t2 = time.time()
     result = {"args": vars(args), "prediction": prediction, "per_image": rows, **summarize(rows)}
     if args.val_batches > 0:
-        result["val_loss"] = val_loss(model, cfg, args, dev, prediction)
+        result["val_loss"], bins = val_loss(model, cfg, args, dev, prediction)
+        if bins is not None:
+            result["val_loss_bins"] = bins
     result["sample_seconds"] = t2 - t1
     result["wall_seconds"] = time.time() - t0
     tmp = os.path.join(args.out, "metrics.json.tmp")
