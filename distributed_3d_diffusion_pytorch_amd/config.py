@@ -55,6 +55,9 @@ class DataConfig:
     index: str = ""                  # pickle/json index {instance: [views]}; "" = scan
     imgsize: int = 64
     synthetic: bool = False          # on-device synthetic SRN-shaped batches
+    procedural: bool = False         # on-device ray-cast procedural scenes (data/procedural.py)
+    procedural_objects: int = 0      # object ids [0, N) (0 = [0, 2^31)); ids with id % 10 == 9 are held out
+    procedural_views: int = 50       # views per object
     num_workers: int = 4
     cache: str = ""                  # preprocessed uint8 cache (.npz dir), "" = PNG path
     seed: int = 0

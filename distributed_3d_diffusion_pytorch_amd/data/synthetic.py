@@ -94,9 +94,16 @@ def random_orbit_poses(n: int, generator: torch.Generator, device, radius: float
     """Batched look-at cam-to-world poses (float64): R [n,3,3], t [n,3]."""
     az = torch.rand(n, generator=generator, device=device, dtype=torch.float64) * 2 * math.pi
     el = 0.05 + torch.rand(n, generator=generator, device=device, dtype=torch.float64) * 0.95
+    return orbit_look_at(az, el, radius)
+
+
+def orbit_look_at(az: torch.Tensor, el: torch.Tensor, radius: float = SRN_RADIUS
+                  ) -> Tuple[torch.Tensor, torch.Tensor]:
+    """The look-at pose (OpenCV cam-to-world, z up) on the orbit at azimuth
+    ``az`` and elevation ``el`` (float64 [n]): R [n,3,3], t [n,3]."""
     pos = radius * torch.stack([torch.cos(el) * torch.cos(az), torch.cos(el) * torch.sin(az), torch.sin(el)], -1)
     fwd = -pos / pos.norm(dim=-1, keepdim=True)
-    up = torch.tensor([0.0, 0.0, 1.0], dtype=torch.float64, device=device).expand_as(fwd)
+    up = torch.tensor([0.0, 0.0, 1.0], dtype=torch.float64, device=pos.device).expand_as(fwd)
     right = torch.linalg.cross(fwd, up)
     right = right / right.norm(dim=-1, keepdim=True)
     down = torch.linalg.cross(fwd, right)

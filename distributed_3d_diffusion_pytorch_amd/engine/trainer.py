@@ -385,8 +385,8 @@ class Trainer:
 
     def make_val_data(self) -> list:
         """The fixed validation batches of this rank (``cfg.val_batches`` of
-        the rank's batch size, materialised once): synthetic batches with a
-        seed of their own, or the first held-out examples of ``data.val_path``."""
+        the rank's batch size, materialised once): synthetic or procedural
+        (held-out objects) batches with a seed of their own, or the first held-out examples of ``data.val_path``."""
         dc = self.cfg.data
         nb = max(int(self.cfg.val_batches), 1)
         if dc.synthetic:
@@ -394,8 +394,14 @@ class Trainer:
             it = SyntheticBatches(self.local_batch, dc.imgsize, self.device,
                                   seed=dc.seed * 7919 + self.ctx.rank + 104729)
             return [next(it) for _ in range(nb)]
+        if dc.procedural:
+            from ..data import ProceduralBatches
+            it = ProceduralBatches(self.local_batch, dc.imgsize, self.device, seed=dc.seed * 7919 + 104729,
+                                   objects=dc.procedural_objects, views=dc.procedural_views, split="val",
+                                   example_offset=self.ctx.rank * self.local_batch)
+            return [next(it) for _ in range(nb)]
         if not dc.val_path:
-            raise ValueError("val_every > 0 needs data.val_path (train.py --val_data) or synthetic data")
+            raise ValueError("val_every > 0 needs data.val_path (train.py --val_data), synthetic or procedural data")
         from ..data import SRNDataset, ShardSampler, collate
         index =dc.index if os.path.abspath(dc.val_path) == os.path.abspath(dc.path) else ""
         ds = SRNDataset("val", dc.val_path, index, dc.imgsize, seed=dc.seed)
@@ -411,6 +417,13 @@ class Trainer:
             from ..data import SyntheticBatches
             it = SyntheticBatches(self.local_batch, dc.imgsize, self.device,
                                   seed=dc.seed * 7919 + self.ctx.rank)
+            return it, None, None
+        if dc.procedural:
+            # one global batch per step, drawn from (seed, step, global example): the rank renders its own rows
+            from ..data import ProceduralBatches
+            it = ProceduralBatches(self.local_batch, dc.imgsize, self.device, seed=dc.seed * 7919,
+                                   objects=dc.procedural_objects, views=dc.procedural_views, split="train",
+                                   example_offset=self.ctx.rank * self.local_batch)
             return it, None, None
         from ..data import SRNDataset, ShardSampler, MultiEpochsDataLoader, CachedSRNDataset, CachedBatchLoader
         if dc.cache:

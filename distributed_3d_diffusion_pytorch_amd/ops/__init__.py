@@ -233,6 +233,23 @@ def image_metrics(pred, target, quantize: bool = True):
     return _t.image_metrics(pred, target, quantize)
 
 
+def scene_render(table, R, t, K, H: int, W: int, *, aa: int = 3, return_aux: bool = False):
+    """Ray-cast images ``[N,3,H,W]`` fp32 in [-1, 1] of procedural scenes
+    (``data.procedural``): ``table`` fp64 [N,6,16] (per primitive slot the
+    world-to-unit map A [9], centre [3], albedo [3], kind 0 empty / 1 ellipsoid
+    / 2 box), cameras ``R`` [N,3,3] cam-to-world, ``t`` [N,3] and ``K`` [N,3,3]
+    fp64, ``K`` the intrinsics of the 128 x 128 image (the op rescales it to
+    ``H`` x ``W`` as ``camera_rays(..., rescale_from=128)`` does).  A pixel is
+    the mean of ``aa`` x ``aa`` sub-pixel rays (1..4); the background is white.
+    ``return_aux``: also ``depth`` [N,H,W] fp32 (+inf on a miss) and ``prim``
+    [N,H,W] int32 (-1 on a miss) of the pixel-centre ray.  HIP
+    (``csrc/scene.hip``) on the GPU, the float64 torch form on the CPU."""
+    _t.scene_render_check(table, R, t, K, H, W, aa)
+    if table.is_cuda and table.shape[0] > 0 and use_hip(table, any_dtype=True):
+        return _h().scene_render(table, R, t, K, H, W, aa=aa, return_aux=return_aux)
+    return _t.scene_render(table, R, t, K, H, W, aa=aa, return_aux=return_aux)
+
+
 def psnr(mse):
     """``10 log10(1 / mse)`` on the [0, 1] scale; ``+inf`` where ``mse == 0``."""
     return -10.0 * torch.log10(torch.as_tensor(mse, dtype=torch.float32))
@@ -244,7 +261,7 @@ posenc_nerf = _t.posenc_nerf
 
 __all__ = ["diffusion_inputs", "diff_loss_nhwc", "diff_loss_rows", "loss_bins_add", "group_norm", "gn_film", "conv3x3", "linear", "film_batch", "cat_gn_silu_dense", "cond_conv", "ray_posenc_dir",
            "ray_origin_pe", "ray_conditioning", "attention", "avgpool2", "upsample2",
-           "silu", "logsnr_mlp", "ray_posenc", "image_metrics", "psnr", "posenc_ddpm", "camera_rays", "posenc_nerf", "set_backend",
+           "silu", "logsnr_mlp", "ray_posenc", "image_metrics", "scene_render", "psnr", "posenc_ddpm", "camera_rays", "posenc_nerf", "set_backend",
            "use_hip", "load_library", "library_error", "lib_path"]
 
 

@@ -123,6 +123,8 @@ SIGNATURES = {
     "d3d_loss_bins": [P, I, P, P, I, I, I, C.c_double, C.c_double, C.c_double, P],
     # metrics.hip (taps: 11 host doubles)
     "d3d_image_metrics": [P, P, I, I, I, I, I, C.POINTER(C.c_double), P, P, P],
+    # scene.hip
+    "d3d_scene_render": [P, P, P, P, I, I, I, I, I, P, P, P, P],
 }
 
 

@@ -2886,3 +2886,21 @@ def image_metrics(pred, target, quantize=True):
     _chk(_lib.d3d_image_metrics(x.data_ptr(), y.data_ptr(), N, C, H, W, int(bool(quantize)), _SSIM_TAPS,
                                 part.data_ptr(), out.data_ptr(), _st()), "image_metrics")
     return out[:, 0], out[:, 1]
+
+
+# ---------------------------------------------------- procedural scenes ---
+def scene_render(table, R, t, K, H, W, *, aa=3, return_aux=False):
+    """img [N,3,H,W] fp32 (and, with ``return_aux``, depth [N,H,W] fp32 and
+    prim [N,H,W] int32) of the fp64 scene tables under the fp64 cameras
+    (csrc/scene.hip: one thread per pixel, fp64, one launch; the numbers of
+    ``torch_impl.scene_render``).  Graph-capturable."""
+    N = _t.scene_render_check(table, R, t, K, H, W, aa)
+    table, R, t, K = table.contiguous(), R.contiguous(), t.contiguous(), K.contiguous()
+    dev = table.device
+    img = torch.empty(N, 3, H, W, dtype=F32, device=dev)
+    depth = torch.empty(N, H, W, dtype=F32, device=dev) if return_aux else None
+    prim = torch.empty(N, H, W, dtype=torch.int32, device=dev) if return_aux else None
+    if N > 0:
+        _chk(_lib.d3d_scene_render(table.data_ptr(), R.data_ptr(), t.data_ptr(), K.data_ptr(), N, H, W, aa,
+                                   _t.SCENE_REF, img.data_ptr(), _ptr(depth), _ptr(prim), _st()), "scene_render")
+    return (img, depth, prim) if return_aux else img

@@ -483,3 +483,144 @@ def image_metrics(pred: torch.Tensor, target: torch.Tensor, quantize: bool = Tru
     vx, vy, cxy = blur(x * x) - mx * mx, blur(y * y) - my * my, blur(x * y) - mx * my
     s = ((2 * mx * my + SSIM_C1) * (2 * cxy + SSIM_C2)) / ((mx * mx + my * my + SSIM_C1) * (vx + vy + SSIM_C2))
     return mse.float(), s.reshape(N, -1).mean(1).float()
+
+
+# ---------------------------------------------------- procedural scenes ---
+# The analytic ray caster of data/procedural.py (csrc/scene.hip holds the rule
+# in full).  fp64 throughout, written operation by operation in the order the
+# kernel uses, so the two agree to rounding.
+SCENE_SLOTS, SCENE_WORDS = 6, 16
+SCENE_REF = 128                      # K is the intrinsics of the 128 x 128 SRN image
+SCENE_LIGHT = (0.3, 0.2, 1.0)
+SCENE_AMBIENT, SCENE_DIFFUSE = 0.35, 0.65
+
+
+def scene_render_check(table, R, t, K, H, W, aa) -> int:
+    """Argument check shared by both backends (ValueError); returns N."""
+    if table.dim() != 3 or tuple(table.shape[1:]) != (SCENE_SLOTS, SCENE_WORDS):
+        raise ValueError(f"scene_render: table must be [N,{SCENE_SLOTS},{SCENE_WORDS}], got {tuple(table.shape)}")
+    N = table.shape[0]
+    for name, x, shape in (("R", R, (N, 3, 3)), ("t", t, (N, 3)), ("K", K, (N, 3, 3))):
+        if tuple(x.shape) != shape:
+            raise ValueError(f"scene_render: {name} must be {list(shape)} for {N} images, got {tuple(x.shape)}")
+    for name, x in (("table", table), ("R", R), ("t", t), ("K", K)):
+        if x.dtype != torch.float64:
+            raise ValueError(f"scene_render: {name} must be float64, got {x.dtype}")
+        if x.device != table.device:
+            raise ValueError(f"scene_render: {name} is on {x.device}, the table on {table.device}")
+    for name, v in (("H", H), ("W", W), ("aa", aa)):
+        if isinstance(v, bool) or not isinstance(v, int):
+            raise ValueError(f"scene_render: {name} must be an int, got {v!r}")
+    if H < 1 or W < 1:
+        raise ValueError(f"scene_render: H, W must be positive, got {H} x {W}")
+    if not 1 <= aa <= 4:
+        raise ValueError(f"scene_render: aa must be in 1..4, got {aa}")
+    return N
+
+
+def _inv3(M: torch.Tensor) -> torch.Tensor:
+    """Inverse of [N,3,3] by the adjugate (scene_render_k's expression)."""
+    a, b, c, d, e, f, g, h, i = (M[:, r, s] for r in range(3) for s in range(3))
+    A, B, C = e * i - f * h, f * g - d * i, d * h - e * g
+    det = a * A + b * B + c * C
+    adj = [A, c * h - b * i, b * f - c * e, B, a * i - c * g, c * d - a * f, C, b * g - a * h, a * e - b * d]
+    return torch.stack([x / det for x in adj], -1).reshape(-1, 3, 3)
+
+
+def _scene_prims(table, t):
+    """Per slot (A [N,3,3], the origin in the primitive's frame A (t - c) as 3
+    x [N], albedo [N,3], kind [N] int64)."""
+    N = table.shape[0]
+    prims = []
+    for p in range(SCENE_SLOTS):
+        A = table[:, p, :9].reshape(N, 3, 3)
+        x = [t[:, k] - table[:, p, 9 + k] for k in range(3)]
+        o = [A[:, k, 0] * x[0] + A[:, k, 1] * x[1] + A[:, k, 2] * x[2] for k in range(3)]
+        prims.append((A, o, table[:, p, 12:15], table[:, p, 15].to(torch.int64)))
+    return prims
+
+
+def _scene_dirs(Kinv, R, u, v):
+    """World directions (3 x [N,H,W]) through pixel coordinates ``u``, ``v`` [H,W]."""
+    e = lambda x: x[:, None, None]  # noqa: E731
+    c = [e(Kinv[:, k, 0]) * u + e(Kinv[:, k, 1]) * v + e(Kinv[:, k, 2]) for k in range(3)]
+    nrm = torch.sqrt(c[0] * c[0] + c[1] * c[1] + c[2] * c[2])
+    c = [x / nrm for x in c]
+    return [e(R[:, k, 0]) * c[0] + e(R[:, k, 1]) * c[1] + e(R[:, k, 2]) * c[2] for k in range(3)]
+
+
+def scene_trace(table: torch.Tensor, origin: torch.Tensor, dirs: torch.Tensor):
+    """Nearest hits of arbitrary rays, in float64: ``table`` [N,6,16],
+    ``origin`` [N,3], unit ``dirs`` [N,H,W,3] -> (t [N,H,W], +inf on a miss;
+    prim [N,H,W] int64, -1 on a miss; colour [N,3,H,W] in [0, 1])."""
+    return _scene_hit(_scene_prims(table, origin), list(dirs.unbind(-1)))
+
+
+def _scene_hit(prims, d):
+    e = lambda x: x[:, None, None]  # noqa: E731
+    inf = torch.full_like(d[0], float("inf"))
+    best_t, best_p = inf, torch.full(d[0].shape, -1, dtype=torch.int64, device=d[0].device)
+    n = [torch.zeros_like(d[0]) for _ in range(3)]
+    zero, one = torch.zeros_like(d[0]), torch.ones_like(d[0])
+    for p, (A, o, _, kind) in enumerate(prims):
+        q = [e(A[:, k, 0]) * d[0] + e(A[:, k, 1]) * d[1] + e(A[:, k, 2]) * d[2] for k in range(3)]
+        ob = [e(x) + zero for x in o]
+        # ellipsoid: the near root of |o + t q|^2 = 1
+        qa = q[0] * q[0] + q[1] * q[1] + q[2] * q[2]
+        qb = ob[0] * q[0] + ob[1] * q[1] + ob[2] * q[2]
+        qc = ob[0] * ob[0] + ob[1] * ob[1] + ob[2] * ob[2] - 1.0
+        disc = qb * qb - qa * qc
+        t_e = (-qb - torch.sqrt(disc.clamp_min(0.0))) / qa
+        m_e = [ob[k] + t_e * q[k] for k in range(3)]
+        # box: slabs of [-1, 1]^3, the entry face's normal
+        t1 = torch.stack([(-1.0 - ob[k]) * (1.0 / q[k]) for k in range(3)], -1)
+        t2 = torch.stack([(1.0 - ob[k]) * (1.0 / q[k]) for k in range(3)], -1)
+        tmin, ax = torch.minimum(t1, t2).max(-1)
+        tmax = torch.maximum(t1, t2).min(-1).values
+        qs = torch.stack(q, -1).gather(-1, ax[..., None])[..., 0]
+        sg = torch.where(qs > 0.0, -one, one)
+        m_b = [torch.where(ax == k, sg, zero) for k in range(3)]
+        is_e, is_b = e(kind == 1), e(kind == 2)
+        tt = torch.where(is_e, t_e, tmin)
+        hit = ((is_e & (disc > 0.0)) | (is_b & (tmin < tmax))) & (tt > 0.0) & (tt < best_t)
+        best_t = torch.where(hit, tt, best_t)
+        best_p = torch.where(hit, torch.full_like(best_p, p), best_p)
+        n = [torch.where(hit, torch.where(is_e, m_e[k], m_b[k]), n[k]) for k in range(3)]
+    ln = math.sqrt(sum(x * x for x in SCENE_LIGHT))
+    col = [one, one, one]
+    for p, (A, _, alb, _) in enumerate(prims):
+        w = [e(A[:, 0, k]) * n[0] + e(A[:, 1, k]) * n[1] + e(A[:, 2, k]) * n[2] for k in range(3)]
+        wn = torch.sqrt(w[0] * w[0] + w[1] * w[1] + w[2] * w[2])
+        w = [x / wn for x in w]
+        ndl = w[0] * (SCENE_LIGHT[0] / ln) + w[1] * (SCENE_LIGHT[1] / ln) + w[2] * (SCENE_LIGHT[2] / ln)
+        shade = SCENE_AMBIENT + SCENE_DIFFUSE * ndl.clamp_min(0.0)
+        col = [torch.where(best_p == p, e(alb[:, k]) * shade, col[k]) for k in range(3)]
+    return best_t, best_p, torch.stack(col, 1)
+
+
+def scene_render(table: torch.Tensor, R: torch.Tensor, t: torch.Tensor, K: torch.Tensor, H: int, W: int, *,
+                 aa: int = 3, return_aux: bool = False):
+    """Images [N,3,H,W] fp32 in [-1, 1] of the scene tables [N,6,16] (fp64; per
+    slot A [9], centre [3], albedo [3], kind) under the cameras ``R`` [N,3,3]
+    cam-to-world, ``t`` [N,3] and ``K`` [N,3,3], the intrinsics of the 128 x
+    128 image (``camera_rays(..., rescale_from=128)`` gives the pixel-centre
+    rays).  A pixel is the mean of ``aa`` x ``aa`` sub-pixel rays.
+    ``return_aux``: also depth [N,H,W] fp32 (+inf on a miss) and prim [N,H,W]
+    int32 (-1 on a miss) of the pixel-centre ray.  The rule is stated in
+    csrc/scene.hip; this float64 form is the CPU path and the kernel's oracle."""
+    N = scene_render_check(table, R, t, K, H, W, aa)
+    dt, dev = torch.float64, table.device
+    s = torch.tensor([W / SCENE_REF, H / SCENE_REF, 1.0], dtype=dt, device=dev)
+    Kinv = _inv3(K * s[None, :, None])
+    prims = _scene_prims(table, t)
+    py, px = torch.meshgrid(torch.arange(H, dtype=dt, device=dev), torch.arange(W, dtype=dt, device=dev),
+                            indexing="ij")
+    acc = torch.zeros(N, 3, H, W, dtype=dt, device=dev)
+    for i in range(aa):
+        for j in range(aa):
+            acc = acc + _scene_hit(prims, _scene_dirs(Kinv, R, px + (j + 0.5) / aa, py + (i + 0.5) / aa))[2]
+    img = (2.0 * (acc / float(aa * aa)) - 1.0).float()
+    if not return_aux:
+        return img
+    depth, prim, _ = _scene_hit(prims, _scene_dirs(Kinv, R, px + 0.5, py + 0.5))
+    return img, depth.float(), prim.to(torch.int32)

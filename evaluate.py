@@ -3,6 +3,7 @@
 (the 3DiM protocol) and, optionally, the held-out training loss.
 
     python evaluate.py --model runs/cars64/latest.pt --data data/SRN/cars_train --instances 64
+    python evaluate.py --model runs/proc64/latest.pt --procedural --instances 64
 
 Takes the first ``--instances`` objects of the split (the 90 / 10 rule of the
 training set), conditions on ``--input_view`` of each and generates the views
@@ -13,7 +14,9 @@ listed in ``--views``, one chain per (object, guidance weight); up to
 view alone.  The results are scored on the device as the 8-bit PNGs would be,
 and ``<out>/metrics.json`` gets the arguments, one row per (instance, view, w)
 and the per-w means.  ``--save_png`` also writes
-``<out>/<instance>/<view>/{gt,<w>}.png``.  Single process.
+``<out>/<instance>/<view>/{gt,<w>}.png``.  ``--procedural`` scores the held-out
+objects of the ray-cast procedural scenes against their exact renders instead
+of an SRN tree.  Single process.
 """
 from __future__ import annotations
 
@@ -31,6 +34,12 @@ def parse(argv=None):
     ap.add_argument("--model", default="./trained_model.pt")
     ap.add_argument("--data", default="./data/SRN/cars_train", help="SRN instance root")
     ap.add_argument("--index", default="", help="index pickle/json {instance: [views]}; default: scan --data")
+    ap.add_argument("--procedural", action="store_true",
+                    help="score ray-cast procedural objects (data/procedural.py) instead of --data: the first "
+                         "--instances objects of the split, --views are view ids")
+    ap.add_argument("--proc_seed", type=int, default=0, help="--procedural: the scene family's seed")
+    ap.add_argument("--proc_objects", type=int, default=0,
+                    help="--procedural: object ids [0, N) (0 = [0, 2^31)); ids with id %% 10 == 9 are the val split")
     ap.add_argument("--split", default="val", choices=["train", "val"])
     ap.add_argument("--instances", type=int, default=64, help="first N objects of the split (0 = all)")
     ap.add_argument("--input_view", type=int, default=0)
@@ -70,12 +79,18 @@ def val_loss(model, cfg, args, dev, prediction: str):
     from distributed_3d_diffusion_pytorch_amd.diffusion import loss_bins_report
     from distributed_3d_diffusion_pytorch_amd.data import SRNDataset, collate
     from distributed_3d_diffusion_pytorch_amd.engine import heldout_loss
-    ds = SRNDataset(args.split, args.data, args.index, args.imgsize, seed=args.seed)
-    n = min(len(ds), args.val_batches * args.val_batch_size)
-    if n == 0:
-        raise ValueError(f"no instances in the {args.split} split of {args.data}")
-    batches = (tuple(t.to(dev) for t in collate([ds[i] for i in range(s, min(s + args.val_batch_size, n))]))
-               for s in range(0, n, args.val_batch_size))
+    if args.procedural:
+        import itertools
+        from distributed_3d_diffusion_pytorch_amd.data import ProceduralBatches
+        batches = itertools.islice(ProceduralBatches(args.val_batch_size, args.imgsize, dev, seed=args.proc_seed,
+                                                     objects=args.proc_objects, split=args.split), args.val_batches)
+    else:
+        ds = SRNDataset(args.split, args.data, args.index, args.imgsize, seed=args.seed)
+        n = min(len(ds), args.val_batches * args.val_batch_size)
+        if n == 0:
+            raise ValueError(f"no instances in the {args.split} split of {args.data}")
+        batches = (tuple(t.to(dev) for t in collate([ds[i] for i in range(s, min(s + args.val_batch_size, n))]))
+                   for s in range(0, n, args.val_batch_size))
     dc = dataclasses.replace(cfg.diffusion if cfg is not None else DiffusionConfig(), prediction=prediction)
     table = torch.zeros(args.loss_bins, 5, dtype=torch.float64, device=dev) if args.loss_bins > 0 else None
     loss = float(heldout_loss(model, batches, args.seed, dc, model.compute_dtype, bins=table))
@@ -97,8 +112,13 @@ def run(args) -> dict:
     model, cfg = load_model(args.model, args.imgsize, dev, args.ema)
     prediction = resolve_prediction(args.prediction, cfg)
     print(f"[evaluate] prediction {prediction}", flush=True)
-    objects = load_objects(args.data, args.index, args.split, args.instances, args.imgsize,
-                           sorted({args.input_view, *views}))
+    if args.procedural:
+        from distributed_3d_diffusion_pytorch_amd.data import procedural_objects
+        objects = procedural_objects(args.proc_seed, args.instances, sorted({args.input_view, *views}), args.imgsize,
+                                     objects=args.proc_objects, split=args.split, device=dev)
+    else:
+        objects = load_objects(args.data, args.index, args.split, args.instances, args.imgsize,
+                               sorted({args.input_view, *views}))
     if not objects:
         raise ValueError(f"no instances in the {args.split} split of {args.data}")
     os.makedirs(args.out, exist_ok=True)
@@ -121,7 +141,8 @@ def run(args) -> dict:
     if dev.type == "cuda":
         torch.cuda.synchronize(dev)
     t2 = time.time()
-    result = {"args": vars(args), "prediction": prediction, "per_image": rows, **summarize(rows)}
+    data = f"procedural seed={args.proc_seed} objects={args.proc_objects}" if args.procedural else args.data
+    result = {"args": vars(args), "data": data, "prediction": prediction, "per_image": rows, **summarize(rows)}
     if args.val_batches > 0:
         result["val_loss"], bins = val_loss(model, cfg, args, dev, prediction)
         if bins is not None:

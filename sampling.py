@@ -35,6 +35,10 @@ def parse(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--model", default="./trained_model.pt")
     ap.add_argument("--target", default="./data/SRN/cars_train/a4d535e1b1d3c153ff23af07d9064736")
+    ap.add_argument("--procedural", type=int, default=-1, metavar="OBJECT_ID",
+                    help="sample this object of the ray-cast procedural scenes (data/procedural.py) instead of --target")
+    ap.add_argument("--proc_seed", type=int, default=0, help="--procedural: the scene family's seed")
+    ap.add_argument("--proc_views", type=int, default=8, help="--procedural: views 0 .. V-1 of the object")
     ap.add_argument("--out", default="sampling")
     ap.add_argument("--imgsize", type=int, default=64)
     ap.add_argument("--timesteps", type=int, default=256)
@@ -72,6 +76,15 @@ def load_instance(target: str, imgsize: int):
     return np.stack(imgs), np.stack(Rs), np.stack(Ts), K
 
 
+def procedural_instance(object_id: int, seed: int, views: int, imgsize: int, device):
+    """Views ``0 .. views - 1`` of a procedural object, in :func:`load_instance`'s layout."""
+    from distributed_3d_diffusion_pytorch_amd.data.procedural import render_views, srn_intrinsics
+    if views < 2:
+        raise ValueError(f"--proc_views must be at least 2, got {views}")
+    img, R, t, _ = render_views(seed, [object_id] * views, list(range(views)), imgsize, device)
+    return img.cpu().numpy(), R.cpu().numpy(), t.cpu().numpy(), srn_intrinsics().numpy()
+
+
 def save_png(arr_chw: np.ndarray, path: str) -> None:
     from PIL import Image
     img = ((np.clip(arr_chw.transpose(1, 2, 0), -1, 1) + 1) * 127.5).astype(np.uint8)
@@ -90,7 +103,10 @@ def run(args) -> None:
     dev = ctx.device
     if args.backend != "auto":
         ops.set_backend(args.backend)
-    imgs, Rs, Ts, K = load_instance(args.target, args.imgsize)
+    if args.procedural >= 0:
+        imgs, Rs, Ts, K = procedural_instance(args.procedural, args.proc_seed, args.proc_views, args.imgsize, dev)
+    else:
+        imgs, Rs, Ts, K = load_instance(args.target, args.imgsize)
     model, cfg = load_model(args.model, args.imgsize, dev, args.ema)
     prediction = resolve_prediction(args.prediction, cfg)
     if ctx.is_main:
@@ -143,7 +159,8 @@ def run(args) -> None:
             print(f"[sampling] view {k}/{nviews - 1}: {time.time() - t0:.2f}s", flush=True)
     if args.metrics and ctx.is_main:
         with open(os.path.join(args.out, "metrics.json"), "w") as f:
-            json.dump({"target": args.target, "sampler": args.sampler, "eta": args.eta, "spacing": args.spacing,
+            target = f"proc-{args.proc_seed}-{args.procedural}" if args.procedural >= 0 else args.target
+            json.dump({"target": target, "sampler": args.sampler, "eta": args.eta, "spacing": args.spacing,
                        "prediction": prediction, "per_image": rows}, f, indent=1, allow_nan=False)
     cleanup()
 

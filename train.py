@@ -32,11 +32,17 @@ def parse(argv=None):
     ap.add_argument("--index", default="", help="index pickle/json {instance: [views]}; default <data>/cars.pickle")
     ap.add_argument("--preset", default="", help="config preset (chairs32_cpu, cars64_8gpu, ...)")
     ap.add_argument("--synthetic", action="store_true", help="on-device synthetic SRN-shaped data")
+    ap.add_argument("--procedural", action="store_true",
+                    help="on-device ray-cast procedural scenes: learnable, 3D-consistent data that needs no files "
+                         "(data.procedural_objects=N data.procedural_views=V)")
     ap.add_argument("--gpus", type=int, default=0, help="self-spawn this many local ranks")
     ap.add_argument("--steps", type=int, default=0, help="stop after this many optimizer steps")
     ap.add_argument("--out_dir", default="")
     ap.add_argument("overrides", nargs="*", help="key=value config overrides")
-    return ap.parse_args(argv)
+    args = ap.parse_args(argv)
+    if args.procedural and args.synthetic:
+        ap.error("--procedural and --synthetic are mutually exclusive")
+    return args
 
 
 def run(args) -> None:
@@ -61,6 +67,10 @@ def run(args) -> None:
         cfg.data.val_path = args.val_data
     if args.synthetic:
         cfg.data.synthetic = True
+    if args.procedural:
+        cfg.data.procedural = True
+    if cfg.data.procedural and cfg.data.synthetic:
+        raise ValueError("data.procedural and data.synthetic are mutually exclusive")
     if args.transfer:
         cfg.transfer = args.transfer
     if args.out_dir:
@@ -72,7 +82,7 @@ def run(args) -> None:
         cfg.dtype = "fp32"
     if ctx.is_main:
         print(f"[train] world={ctx.world} device={ctx.device} global_batch={cfg.global_batch} "
-              f"img={cfg.model.H} data={'synthetic' if cfg.data.synthetic else cfg.data.path} "
+              f"img={cfg.model.H} data={'synthetic' if cfg.data.synthetic else 'procedural' if cfg.data.procedural else cfg.data.path} "
               f"prediction={cfg.diffusion.prediction} loss_weight={cfg.diffusion.loss_weight}", flush=True)
     try:
         trainer = Trainer(cfg, ctx)
