@@ -180,7 +180,8 @@ def procedural_objects(seed: int, instances: int, views: Sequence[int], imgsize:
                        split: str = "val", aa: int = 3, device=None) -> List:
     """The first ``instances`` objects of the split with the listed views, as
     the ``EvalObject`` list ``engine.evaluate_objects`` and the sampler take
-    (CPU fp32 tensors, names ``proc-<seed>-<id>``).  Rendered on ``device``
+    (CPU fp32 tensors, names ``proc-<seed>-<id>``; ``scene`` is the object's
+    fp64 table, which the geometry-aware scores read).  Rendered on ``device``
     (default: the GPU when there is one)."""
     from ..engine.evaluate import EvalObject
     n = split_size(objects, split)
@@ -197,9 +198,11 @@ def procedural_objects(seed: int, instances: int, views: Sequence[int], imgsize:
     img, R, t, _ = render_views(seed, [o for o in ids for _ in views], views * len(ids), imgsize, device, aa)
     img, R, t = img.cpu(), R.float().cpu(), t.float().cpu()
     K = srn_intrinsics().float()
+    scene = procedural_scene(seed, ids)                 # the geometry, for the geometry-aware scores
     return [EvalObject(f"proc-{seed}-{o}", {v: img[j * nv + i] for i, v in enumerate(views)},
                        {v: R[j * nv + i] for i, v in enumerate(views)},
-                       {v: t[j * nv + i] for i, v in enumerate(views)}, K.clone()) for j, o in enumerate(ids)]
+                       {v: t[j * nv + i] for i, v in enumerate(views)}, K.clone(), scene=scene[j].clone())
+            for j, o in enumerate(ids)]
 
 
 def to_uint8(img: torch.Tensor) -> np.ndarray:

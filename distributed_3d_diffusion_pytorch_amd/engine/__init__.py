@@ -1,7 +1,9 @@
 from .optim import FusedAdam, ema_decay_for, warmup_lr
 from .trainer import Trainer
 from .sampler import DiffusionSampler, RecordEntry, SolverState, shard_range
-from .evaluate import EvalObject, evaluate_objects, heldout_loss, load_objects, summarize
+from .evaluate import (EvalObject, evaluate_objects, gt_ceiling, heldout_loss, load_objects, summarize,
+                       summarize_consistency)
 
 __all__ = ["FusedAdam", "ema_decay_for", "warmup_lr", "Trainer", "DiffusionSampler", "RecordEntry", "SolverState",
-           "shard_range", "EvalObject", "evaluate_objects", "heldout_loss", "load_objects", "summarize"]
+           "shard_range", "EvalObject", "evaluate_objects", "heldout_loss", "load_objects", "summarize",
+           "summarize_consistency", "gt_ceiling"]

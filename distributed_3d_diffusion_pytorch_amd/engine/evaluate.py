@@ -8,7 +8,10 @@ input view alone.  Up to ``batch`` objects run as ONE graph-replayed sampler
 step (:meth:`DiffusionSampler.sample_groups`: one chain per (object, guidance
 weight), the conditioning computed once per object and class), and the results
 are scored on the device by ``ops.image_metrics(quantize=True)``, i.e. exactly
-as the PNGs a writer would store.  Single process.
+as the PNGs a writer would store.  Objects that carry their geometry (the
+procedural scenes) can also be scored with it: ``ops.view_consistency`` splits
+every generated view into background, disoccluded and co-visible pixels and
+measures how well the views reproject into each other.  Single process.
 """
 from __future__ import annotations
 
@@ -73,11 +76,14 @@ def heldout_loss(model, batches: Iterable, seed: int, diffusion_cfg, dtype, bins
 # ------------------------------------------------------------------ objects
 class EvalObject:
     """One object: ``imgs[v]`` [3,H,W] fp32 in [-1, 1], ``R[v]`` [3,3], ``T[v]``
-    [3] for the views v the evaluation touches, and its intrinsics K [3,3]."""
+    [3] for the views v the evaluation touches, and its intrinsics K [3,3].
+    ``scene``: the object's analytic geometry, an fp64 [6,16] table of
+    ``data.procedural`` (None for objects that carry none, such as SRN files);
+    the geometry-aware scores (``consistency=True``) need it."""
 
     def __init__(self, name: str, imgs: Dict[int, torch.Tensor], R: Dict[int, torch.Tensor],
-                 T: Dict[int, torch.Tensor], K: torch.Tensor):
-        self.name, self.imgs, self.R, self.T, self.K = name, imgs, R, T, K
+                 T: Dict[int, torch.Tensor], K: torch.Tensor, scene: Optional[torch.Tensor] = None):
+        self.name, self.imgs, self.R, self.T, self.K, self.scene = name, imgs, R, T, K, scene
 
 
 def load_objects(root: str, index: str = "", split: str = "val", instances: int = 0, imgsize: int = 64,
@@ -108,13 +114,48 @@ def load_objects(root: str, index: str = "", split: str = "val", instances: int 
 
 
 # --------------------------------------------------------------- evaluation
+_CLASSES = ("background", "disoccluded", "covisible")
+
+
+def _ratio(total: float, count: float):
+    """(mse, psnr) of a sum over ``count`` pixels x 3 channels; None where the
+    count or the mse is 0."""
+    if not count > 0 or not total > 0:
+        return None, None
+    mse = total / (3.0 * count)
+    return mse, 10.0 * math.log10(1.0 / mse)
+
+
+def _consistency_fields(st: Sequence[float]) -> dict:
+    """The row fields of one ``ops.view_consistency`` stats row."""
+    out = {"n_background": int(st[0]), "n_disoccluded": int(st[1]), "n_covisible": int(st[2]), "n_clean": int(st[3])}
+    for j, name in enumerate(_CLASSES):
+        out[f"mse_{name}"], out[f"psnr_{name}"] = _ratio(st[4 + j], st[j])
+    out["reproj_mse"], out["reproj_psnr"] = _ratio(st[7], st[3])
+    return out
+
+
+def _scenes(objects: Sequence[EvalObject]) -> None:
+    missing = [o.name for o in objects if getattr(o, "scene", None) is None]
+    if missing:
+        raise ValueError(f"consistency needs every object's scene table (procedural objects carry one); "
+                         f"{len(missing)} of {len(objects)} have none, the first is {missing[0]!r}")
+
+
+def _pose64(objs: Sequence[EvalObject], v: int, dev, rep: int = 1):
+    """(R [G * rep,3,3], T [G * rep,3]) fp64 of view ``v``: the objects' stored values, upcast."""
+    R = torch.stack([o.R[v] for o in objs]).to(dev).double().repeat_interleave(rep, 0)
+    T = torch.stack([o.T[v] for o in objs]).to(dev).double().repeat_interleave(rep, 0)
+    return R, T
+
+
 @torch.no_grad()
 def evaluate_objects(model, objects: Sequence[EvalObject], input_view: int = 0, views: Sequence[int] = (1,),
                      w: Sequence[float] = (3.0,), timesteps: int = 256, batch: int = 64,
                      autoregressive: bool = False, seed: int = 0, device=None, ref_quirk: bool = False,
                      graph: Optional[bool] = None, keep_images: bool = False,
                      on_view: Optional[Callable] = None, solver: str = "ancestral", eta: float = 0.0,
-                     spacing: str = "t", prediction: str = "eps"):
+                     spacing: str = "t", prediction: str = "eps", consistency: bool = False):
     """Generate ``views`` of every object from its ``input_view`` and score
     them.  Returns ``(rows, images)``: one row ``{instance, view, w, chain,
     mse, psnr, ssim}`` per (object, view, w) -- ``chain`` the global chain
@@ -124,11 +165,27 @@ def evaluate_objects(model, objects: Sequence[EvalObject], input_view: int = 0, 
     called with each generated batch ([G * len(w),3,H,W], object-major) and
     its ground truth [G,3,H,W].  ``solver`` / ``eta`` / ``spacing``: the
     update rule and step spacing of :class:`DiffusionSampler`, ``prediction``
-    what the model outputs (eps or v)."""
+    what the model outputs (eps or v).
+
+    ``consistency`` (every object needs a ``scene``, else ValueError): each
+    generated batch also goes through ``ops.view_consistency`` with the input
+    view's ground truth and pose as the source, and every row gains
+    ``n_background`` / ``n_disoccluded`` / ``n_covisible`` / ``n_clean``,
+    ``mse_<class>`` / ``psnr_<class>`` of the generated image against the
+    ground truth on each class's pixels, and ``reproj_mse`` / ``reproj_psnr``
+    of the generated image against the input view warped into it (None where
+    the count or the mse is 0).  The poses are the objects' fp32 values upcast
+    to fp64, what the model was conditioned on.  The function then returns
+    ``(rows, images, pair_rows)``: with more than one view, one ``{instance,
+    w, chain, src_view, tgt_view, n_clean, mse, psnr}`` per ordered pair of
+    generated views of a chain, the reprojection error of one into the other."""
     dev = torch.device(device) if device is not None else next(model.parameters()).device
     nw = len(w)
     rows: List[dict] = []
+    pair_rows: List[dict] = []
     images: Dict[tuple, torch.Tensor] = {}
+    if consistency:
+        _scenes(objects)
     for s in range(0, len(objects), max(int(batch), 1)):
         objs = objects[s:s + max(int(batch), 1)]
         G = len(objs)
@@ -140,6 +197,12 @@ def evaluate_objects(model, objects: Sequence[EvalObject], input_view: int = 0, 
         K = torch.stack([o.K for o in objs]).to(dev)
         records = [[RecordEntry(o.imgs[input_view].to(dev)[None].expand(nw, -1, -1, -1).contiguous(),
                                 o.R[input_view].to(dev), o.T[input_view].to(dev))] for o in objs]
+        if consistency:
+            table = torch.stack([o.scene for o in objs]).to(dev).double().repeat_interleave(nw, 0)
+            K64 = K.double().repeat_interleave(nw, 0)
+            src = torch.stack([o.imgs[input_view] for o in objs]).to(dev).float().repeat_interleave(nw, 0)
+            sR, sT = _pose64(objs, input_view, dev, nw)
+            kept = {}
         for v in views:
             tR = torch.stack([o.R[v] for o in objs]).to(dev)
             tT = torch.stack([o.T[v] for o in objs]).to(dev)
@@ -147,12 +210,18 @@ def evaluate_objects(model, objects: Sequence[EvalObject], input_view: int = 0, 
             gt = torch.stack([o.imgs[v] for o in objs]).to(dev)
             mse, ssim = ops.image_metrics(out, gt.repeat_interleave(nw, 0), quantize=True)
             mse_l, ssim_l = mse.double().cpu().tolist(), ssim.double().cpu().tolist()
+            if consistency:
+                kept[int(v)] = out.contiguous()
+                st_l = ops.view_consistency(table, K64, sR, sT, src, *_pose64(objs, v, dev, nw), kept[int(v)],
+                                            gt.float().repeat_interleave(nw, 0)).cpu().tolist()
             for gi, o in enumerate(objs):
                 for i in range(nw):
                     j = gi * nw + i
                     rows.append({"instance": o.name, "view": int(v), "w": float(w[i]), "chain": s * nw + j,
                                  "mse": mse_l[j], "psnr": 10.0 * math.log10(1.0 / mse_l[j]) if mse_l[j] > 0 else None,
                                  "ssim": ssim_l[j]})
+                    if consistency:
+                        rows[-1].update(_consistency_fields(st_l[j]))
                 if keep_images:
                     images[(o.name, int(v))] = out[gi * nw:(gi + 1) * nw].cpu()
                 if autoregressive:
@@ -160,7 +229,76 @@ def evaluate_objects(model, objects: Sequence[EvalObject], input_view: int = 0, 
                                                    o.T[v].to(dev)))
             if on_view is not None:
                 on_view(objs, int(v), out, gt)
-    return rows, images
+        if consistency:
+            for va in kept:
+                for vb in kept:
+                    if va == vb:
+                        continue
+                    st_l = ops.view_consistency(table, K64, *_pose64(objs, va, dev, nw), kept[va],
+                                                *_pose64(objs, vb, dev, nw), kept[vb]).cpu().tolist()
+                    for gi, o in enumerate(objs):
+                        for i in range(nw):
+                            j = gi * nw + i
+                            m, p = _ratio(st_l[j][7], st_l[j][3])
+                            pair_rows.append({"instance": o.name, "w": float(w[i]), "chain": s * nw + j,
+                                              "src_view": va, "tgt_view": vb, "n_clean": int(st_l[j][3]), "mse": m,
+                                              "psnr": p})
+    return (rows, images, pair_rows) if consistency else (rows, images)
+
+
+def _pool(sel: Sequence[dict], count: str, mse: str) -> dict:
+    """Pooled over rows: the sum of the rows' sums (mse x 3 count) over the sum of 3 count."""
+    n = sum(int(r[count]) for r in sel)
+    total = math.fsum(r[mse] * 3.0 * r[count] for r in sel if r[mse] is not None)
+    m, p = _ratio(total, n)
+    return {"n": n, "mse": m, "psnr": p}
+
+
+def summarize_consistency(rows: Sequence[dict], pair_rows: Sequence[dict] = ()) -> dict:
+    """Per guidance weight the pooled scores of ``evaluate_objects(...,
+    consistency=True)``: ``{"<w>": {name: {n, mse, psnr}}}`` for ``covisible``,
+    ``disoccluded``, ``background`` (generated against ground truth on the
+    class's pixels), ``reproj`` (generated against the warped input view on
+    the clean pixels) and ``pairs`` (generated views against each other).
+    Pooled -- the sum of the rows' sums over the sum of their counts x 3, then
+    the PSNR -- because a single pair may have no clean pixel; ``n`` is the
+    pixel count, ``mse`` / ``psnr`` None where it or the error is 0."""
+    out = {}
+    for wv in sorted({r["w"] for r in rows}):
+        sel = [r for r in rows if r["w"] == wv]
+        d = {name: _pool(sel, f"n_{name}", f"mse_{name}") for name in ("covisible", "disoccluded", "background")}
+        d["reproj"] = _pool(sel, "n_clean", "reproj_mse")
+        d["pairs"] = _pool([r for r in pair_rows if r["w"] == wv], "n_clean", "mse")
+        out[f"{wv:g}"] = d
+    return out
+
+
+@torch.no_grad()
+def gt_ceiling(objects: Sequence[EvalObject], input_view: int = 0, views: Sequence[int] = (1,), device=None) -> dict:
+    """The consistency scores of the ground-truth images themselves, pooled
+    over the objects: ``reproj`` (the input view warped into each of ``views``)
+    and ``pairs`` (every ordered pair of ``views``), each ``{n, mse, psnr}``.
+    This is the interpolation floor of the metric -- a pixel is the mean of
+    its area, the warp a bilinear sample -- not zero error: what a perfect
+    model would score."""
+    _scenes(objects)
+    dev = torch.device(device) if device is not None else torch.device("cpu")
+    table = torch.stack([o.scene for o in objects]).to(dev).double()
+    K64 = torch.stack([o.K for o in objects]).to(dev).double()
+    img = lambda v: torch.stack([o.imgs[v] for o in objects]).to(dev).float().contiguous()  # noqa: E731
+
+    def pooled(pairs):
+        n, total = 0, 0.0
+        for a, b in pairs:
+            st = ops.view_consistency(table, K64, *_pose64(objects, a, dev), img(a), *_pose64(objects, b, dev), img(b))
+            n += int(st[:, 3].sum())
+            total += float(st[:, 7].sum())
+        m, p = _ratio(total, n)
+        return {"n": n, "mse": m, "psnr": p}
+
+    views = [int(v) for v in views]
+    return {"reproj": pooled([(int(input_view), v) for v in views]),
+            "pairs": pooled([(a, b) for a in views for b in views if a != b])}
 
 
 def summarize(rows: Sequence[dict]) -> dict:

@@ -250,6 +250,33 @@ def scene_render(table, R, t, K, H: int, W: int, *, aa: int = 3, return_aux: boo
     return _t.scene_render(table, R, t, K, H, W, aa=aa, return_aux=return_aux)
 
 
+def view_consistency(table, K, R_src, t_src, img_src, R_tgt, t_tgt, img_tgt, ref=None, *,
+                     return_class: bool = False):
+    """Geometry-aware scores of N (source view, target view) pairs of
+    procedural scenes: ``table`` [N,6,16], ``K`` [N,3,3] (the 128 x 128
+    intrinsics, rescaled to the image size as in ``scene_render``), cameras
+    ``R_*`` [N,3,3] cam-to-world and ``t_*`` [N,3], all fp64; ``img_src``,
+    ``img_tgt`` and optionally ``ref`` (the target view's ground truth)
+    ``[N,3,H,W]`` fp32 in [-1, 1], contiguous.  Every target pixel is
+    classified with the scene's true geometry as background (0), disoccluded
+    (1: a surface the source camera does not see), co-visible (2) or clean (3:
+    co-visible with the pixel and its bilinear footprint in the source image
+    on one smooth piece of surface).  Returns ``stats`` [N,8] fp64: the pixel
+    counts of classes 0, 1, 2 (3 counted in 2), the count of clean pixels, the
+    sums of ``((img_tgt - ref) / 2)^2`` over each class's pixels and channels
+    (0 without ``ref``) and the sum of ``((img_tgt - warp) / 2)^2`` over the
+    clean pixels, ``warp`` the source image interpolated at the pixel's
+    reprojection; ``mse = sum / (3 count)``.  ``return_class``: also the class
+    plane ``[N,H,W]`` int32.  HIP (``csrc/consistency.hip``, which states the
+    rule) on the GPU, the float64 torch form on the CPU."""
+    N, H, W = _t.view_consistency_check(table, K, R_src, t_src, img_src, R_tgt, t_tgt, img_tgt, ref)
+    if N == 0:
+        stats = torch.zeros(0, _t.VC_STATS, dtype=torch.float64, device=table.device)
+        return (stats, torch.zeros(0, H, W, dtype=torch.int32, device=table.device)) if return_class else stats
+    impl = _h() if table.is_cuda and use_hip(table, any_dtype=True) else _t
+    return impl.view_consistency(table, K, R_src, t_src, img_src, R_tgt, t_tgt, img_tgt, ref, return_class=return_class)
+
+
 def psnr(mse):
     """``10 log10(1 / mse)`` on the [0, 1] scale; ``+inf`` where ``mse == 0``."""
     return -10.0 * torch.log10(torch.as_tensor(mse, dtype=torch.float32))
@@ -261,7 +288,7 @@ posenc_nerf = _t.posenc_nerf
 
 __all__ = ["diffusion_inputs", "diff_loss_nhwc", "diff_loss_rows", "loss_bins_add", "group_norm", "gn_film", "conv3x3", "linear", "film_batch", "cat_gn_silu_dense", "cond_conv", "ray_posenc_dir",
            "ray_origin_pe", "ray_conditioning", "attention", "avgpool2", "upsample2",
-           "silu", "logsnr_mlp", "ray_posenc", "image_metrics", "scene_render", "psnr", "posenc_ddpm", "camera_rays", "posenc_nerf", "set_backend",
+           "silu", "logsnr_mlp", "ray_posenc", "image_metrics", "scene_render", "view_consistency", "psnr", "posenc_ddpm", "camera_rays", "posenc_nerf", "set_backend",
            "use_hip", "load_library", "library_error", "lib_path"]
 
 

@@ -125,6 +125,8 @@ SIGNATURES = {
     "d3d_image_metrics": [P, P, I, I, I, I, I, C.POINTER(C.c_double), P, P, P],
     # scene.hip
     "d3d_scene_render": [P, P, P, P, I, I, I, I, I, P, P, P, P],
+    # consistency.hip
+    "d3d_view_consistency": [P, P, P, P, P, P, P, P, P, I, I, I, I, P, P, P, P],
 }
 
 

@@ -2904,3 +2904,24 @@ def scene_render(table, R, t, K, H, W, *, aa=3, return_aux=False):
         _chk(_lib.d3d_scene_render(table.data_ptr(), R.data_ptr(), t.data_ptr(), K.data_ptr(), N, H, W, aa,
                                    _t.SCENE_REF, img.data_ptr(), _ptr(depth), _ptr(prim), _st()), "scene_render")
     return (img, depth, prim) if return_aux else img
+
+
+def view_consistency(table, K, R_src, t_src, img_src, R_tgt, t_tgt, img_tgt, ref=None, *, return_class=False):
+    """stats [N,8] fp64 (and, with ``return_class``, the class plane [N,H,W]
+    int32) of N (source, target) pairs over their fp64 scene tables and
+    cameras (csrc/consistency.hip: one thread per target pixel, up to 15 fp64
+    traces, fixed-order block partials and a final sum; the numbers of
+    ``torch_impl.view_consistency``).  Graph-capturable."""
+    N, H, W = _t.view_consistency_check(table, K, R_src, t_src, img_src, R_tgt, t_tgt, img_tgt, ref)
+    table, K = table.contiguous(), K.contiguous()
+    R_src, t_src, R_tgt, t_tgt = R_src.contiguous(), t_src.contiguous(), R_tgt.contiguous(), t_tgt.contiguous()
+    dev = table.device
+    stats = torch.empty(N, _t.VC_STATS, dtype=torch.float64, device=dev)
+    cls = torch.empty(N, H, W, dtype=torch.int32, device=dev) if return_class else None
+    if N > 0:
+        part = torch.empty(N * ((H * W + 255) // 256), _t.VC_STATS, dtype=torch.float64, device=dev)
+        _chk(_lib.d3d_view_consistency(table.data_ptr(), K.data_ptr(), R_src.data_ptr(), t_src.data_ptr(),
+                                       img_src.data_ptr(), R_tgt.data_ptr(), t_tgt.data_ptr(), img_tgt.data_ptr(),
+                                       _ptr(ref), N, H, W, _t.SCENE_REF, part.data_ptr(), stats.data_ptr(), _ptr(cls),
+                                       _st()), "view_consistency")
+    return (stats, cls) if return_class else stats

@@ -556,10 +556,14 @@ def scene_trace(table: torch.Tensor, origin: torch.Tensor, dirs: torch.Tensor):
     return _scene_hit(_scene_prims(table, origin), list(dirs.unbind(-1)))
 
 
-def _scene_hit(prims, d):
+def _scene_nearest(prims, d):
+    """The nearest hit of unit directions ``d`` (3 x [N,H,W]): (t, +inf on a
+    miss; prim int64, -1 on a miss; the normal in the primitive's frame, 3 x
+    [N,H,W]; face int64: 0 on an ellipsoid, 1 + 2 ax + (sg > 0) on a box)."""
     e = lambda x: x[:, None, None]  # noqa: E731
     inf = torch.full_like(d[0], float("inf"))
     best_t, best_p = inf, torch.full(d[0].shape, -1, dtype=torch.int64, device=d[0].device)
+    best_f = torch.zeros_like(best_p)
     n = [torch.zeros_like(d[0]) for _ in range(3)]
     zero, one = torch.zeros_like(d[0]), torch.ones_like(d[0])
     for p, (A, o, _, kind) in enumerate(prims):
@@ -586,6 +590,15 @@ def _scene_hit(prims, d):
         best_t = torch.where(hit, tt, best_t)
         best_p = torch.where(hit, torch.full_like(best_p, p), best_p)
         n = [torch.where(hit, torch.where(is_e, m_e[k], m_b[k]), n[k]) for k in range(3)]
+        face = torch.where(is_e, torch.zeros_like(ax), 1 + 2 * ax + (sg > 0.0).to(ax.dtype))
+        best_f = torch.where(hit, face, best_f)
+    return best_t, best_p, n, best_f
+
+
+def _scene_hit(prims, d):
+    e = lambda x: x[:, None, None]  # noqa: E731
+    best_t, best_p, n, _ = _scene_nearest(prims, d)
+    one = torch.ones_like(d[0])
     ln = math.sqrt(sum(x * x for x in SCENE_LIGHT))
     col = [one, one, one]
     for p, (A, _, alb, _) in enumerate(prims):
@@ -624,3 +637,109 @@ def scene_render(table: torch.Tensor, R: torch.Tensor, t: torch.Tensor, K: torch
         return img
     depth, prim, _ = _scene_hit(prims, _scene_dirs(Kinv, R, px + 0.5, py + 0.5))
     return img, depth.float(), prim.to(torch.int32)
+
+
+# ------------------------------------------------ geometry-aware evaluation ---
+# Co-visible PSNR and reprojection consistency on the procedural scenes
+# (csrc/consistency.hip holds the rule in full).
+VC_STATS = 8
+VC_DEPTH_TOL = 1e-9                  # |tau1 - dist|, the bound of test_views_are_3d_consistent
+
+
+def view_consistency_check(table, K, R_src, t_src, img_src, R_tgt, t_tgt, img_tgt, ref=None):
+    """Argument check shared by both backends (ValueError); returns (N, H, W)."""
+    name = "view_consistency"
+    opt = (("ref", ref),) if ref is not None else ()
+    for nm, x in (("table", table), ("K", K), ("R_src", R_src), ("t_src", t_src), ("img_src", img_src),
+                  ("R_tgt", R_tgt), ("t_tgt", t_tgt), ("img_tgt", img_tgt)) + opt:
+        if not isinstance(x, torch.Tensor):
+            raise ValueError(f"{name}: {nm} must be a tensor, got {type(x).__name__}")
+        if x.device != table.device:
+            raise ValueError(f"{name}: {nm} is on {x.device}, the table on {table.device}")
+    if table.dim() != 3 or tuple(table.shape[1:]) != (SCENE_SLOTS, SCENE_WORDS):
+        raise ValueError(f"{name}: table must be [N,{SCENE_SLOTS},{SCENE_WORDS}], got {tuple(table.shape)}")
+    N = table.shape[0]
+    for nm, x, shape in (("K", K, (N, 3, 3)), ("R_src", R_src, (N, 3, 3)), ("t_src", t_src, (N, 3)),
+                         ("R_tgt", R_tgt, (N, 3, 3)), ("t_tgt", t_tgt, (N, 3))):
+        if tuple(x.shape) != shape:
+            raise ValueError(f"{name}: {nm} must be {list(shape)} for {N} pairs, got {tuple(x.shape)}")
+    for nm, x in (("table", table), ("K", K), ("R_src", R_src), ("t_src", t_src), ("R_tgt", R_tgt), ("t_tgt", t_tgt)):
+        if x.dtype != torch.float64:
+            raise ValueError(f"{name}: {nm} must be float64, got {x.dtype}")
+    if img_tgt.dim() != 4 or img_tgt.shape[0] != N or img_tgt.shape[1] != 3 or min(img_tgt.shape[2:]) < 1:
+        raise ValueError(f"{name}: img_tgt must be [{N},3,H,W], got {tuple(img_tgt.shape)}")
+    for nm, x in (("img_src", img_src), ("img_tgt", img_tgt)) + opt:
+        if x.shape != img_tgt.shape:
+            raise ValueError(f"{name}: {nm} must be {list(img_tgt.shape)} like img_tgt, got {tuple(x.shape)}")
+        if x.dtype != torch.float32:
+            raise ValueError(f"{name}: {nm} must be float32, got {x.dtype}")
+        if not x.is_contiguous():
+            raise ValueError(f"{name}: {nm} must be contiguous")
+    return N, int(img_tgt.shape[2]), int(img_tgt.shape[3])
+
+
+def view_consistency(table, K, R_src, t_src, img_src, R_tgt, t_tgt, img_tgt, ref=None, *, return_class=False):
+    """stats [N,8] fp64 (and, with ``return_class``, the class plane [N,H,W]
+    int32: 0 background, 1 disoccluded, 2 co-visible, 3 clean) of N pairs: the
+    float64 torch form of csrc/consistency.hip, which states the rule.  Every
+    pixel runs all 15 traces; the kernel's early exits only skip work whose
+    result the masks here discard."""
+    N, H, W = view_consistency_check(table, K, R_src, t_src, img_src, R_tgt, t_tgt, img_tgt, ref)
+    dt, dev = torch.float64, table.device
+    e = lambda x: x[:, None, None]  # noqa: E731
+    s = torch.tensor([W / SCENE_REF, H / SCENE_REF, 1.0], dtype=dt, device=dev)
+    Ks = K * s[None, :, None]
+    Kinv = _inv3(Ks)
+    prims_t, prims_s = _scene_prims(table, t_tgt), _scene_prims(table, t_src)
+    py, px = torch.meshgrid(torch.arange(H, dtype=dt, device=dev), torch.arange(W, dtype=dt, device=dev),
+                            indexing="ij")
+
+    def surface(prims, d):
+        t, p, _, f = _scene_nearest(prims, d)
+        return t, torch.where(p >= 0, 8 * p + f, p)
+
+    d = _scene_dirs(Kinv, R_tgt, px + 0.5, py + 0.5)
+    tau, s0 = surface(prims_t, d)
+    hit = s0 >= 0
+    tau = torch.where(hit, tau, torch.zeros_like(tau))              # (a miss: any finite point; masked below)
+    ev = [e(t_tgt[:, k]) + tau * d[k] - e(t_src[:, k]) for k in range(3)]
+    dist = torch.sqrt(ev[0] * ev[0] + ev[1] * ev[1] + ev[2] * ev[2])
+    c = [e(R_src[:, 0, k]) * ev[0] + e(R_src[:, 1, k]) * ev[1] + e(R_src[:, 2, k]) * ev[2] for k in range(3)]
+    kc = [e(Ks[:, k, 0]) * c[0] + e(Ks[:, k, 1]) * c[1] + e(Ks[:, k, 2]) * c[2] for k in range(3)]
+    u, v = kc[0] / kc[2], kc[1] / kc[2]
+    x0, y0 = torch.floor(u - 0.5), torch.floor(v - 0.5)
+    tau1, s1 = surface(prims_s, [x / dist for x in ev])
+    inside = (x0 >= 0.0) & (x0 + 1.0 <= float(W - 1)) & (y0 >= 0.0) & (y0 + 1.0 <= float(H - 1))
+    cov = hit & (c[2] > 0.0) & inside & ((tau1 - dist).abs() < VC_DEPTH_TOL) & (s1 == s0)
+    zero = torch.zeros_like(u)
+    x0, y0 = torch.where(cov, x0, zero), torch.where(cov, y0, zero)    # (elsewhere possibly NaN or outside)
+    fx, fy = torch.where(cov, (u - 0.5) - x0, zero), torch.where(cov, (v - 0.5) - y0, zero)
+    clean = cov
+    for k in range(4):
+        clean = clean & (surface(prims_t, _scene_dirs(Kinv, R_tgt, px + float(k & 1), py + float(k >> 1)))[1] == s0)
+    for k in range(9):
+        clean = clean & (surface(prims_s, _scene_dirs(Kinv, R_src, x0 + float(k % 3), y0 + float(k // 3)))[1] == s0)
+    klass = hit.to(torch.int32) + cov.to(torch.int32) + clean.to(torch.int32)
+
+    tg = img_tgt.double()
+    stats = torch.zeros(N, VC_STATS, dtype=dt, device=dev)
+    masks = [~hit, hit & ~cov, cov]
+    for j, m in enumerate(masks):
+        stats[:, j] = m.flatten(1).sum(1).to(dt)
+    stats[:, 3] = clean.flatten(1).sum(1).to(dt)
+    if ref is not None:
+        se = ((tg - ref.double()) * 0.5).square().sum(1)               # [N,H,W]
+        for j, m in enumerate(masks):
+            stats[:, 4 + j] = torch.where(m, se, zero).flatten(1).sum(1)
+    ix, iy = x0.long(), y0.long()
+    flat = img_src.double().flatten(2)                                 # [N,3,HW]
+
+    def take(dy, dx):                                                  # src at (y0 + dy, x0 + dx), [N,3,H,W]
+        idx = ((iy + dy) * W + ix + dx).clamp(0, H * W - 1).flatten(1)
+        return flat.gather(2, idx[:, None, :].expand(N, 3, H * W)).reshape(N, 3, H, W)
+
+    w00, w01, w10, w11 = (1.0 - fx) * (1.0 - fy), fx * (1.0 - fy), (1.0 - fx) * fy, fx * fy
+    warp = w00[:, None] * take(0, 0) + w01[:, None] * take(0, 1) + w10[:, None] * take(1, 0) + w11[:, None] * take(1, 1)
+    se = ((tg - warp) * 0.5).square().sum(1)
+    stats[:, 7] = torch.where(clean, se, zero).flatten(1).sum(1)
+    return (stats, klass) if return_class else stats

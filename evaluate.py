@@ -16,7 +16,11 @@ and ``<out>/metrics.json`` gets the arguments, one row per (instance, view, w)
 and the per-w means.  ``--save_png`` also writes
 ``<out>/<instance>/<view>/{gt,<w>}.png``.  ``--procedural`` scores the held-out
 objects of the ray-cast procedural scenes against their exact renders instead
-of an SRN tree.  Single process.
+of an SRN tree; there ``--consistency`` adds the geometry-aware scores of
+``ops.view_consistency``: PSNR on the co-visible, disoccluded and background
+pixels, the reprojection error against the input view and between the
+generated views, and the same on the ground truth (``gt_ceiling``).  Single
+process.
 """
 from __future__ import annotations
 
@@ -40,6 +44,9 @@ def parse(argv=None):
     ap.add_argument("--proc_seed", type=int, default=0, help="--procedural: the scene family's seed")
     ap.add_argument("--proc_objects", type=int, default=0,
                     help="--procedural: object ids [0, N) (0 = [0, 2^31)); ids with id %% 10 == 9 are the val split")
+    ap.add_argument("--consistency", action="store_true",
+                    help="--procedural: also score with the scenes' geometry (co-visible / disoccluded / background "
+                         "PSNR, reprojection consistency); metrics.json gets the row fields and a consistency block")
     ap.add_argument("--split", default="val", choices=["train", "val"])
     ap.add_argument("--instances", type=int, default=64, help="first N objects of the split (0 = all)")
     ap.add_argument("--input_view", type=int, default=0)
@@ -103,6 +110,8 @@ def run(args) -> dict:
     from distributed_3d_diffusion_pytorch_amd.engine import evaluate_objects, load_objects, summarize
     from distributed_3d_diffusion_pytorch_amd.engine.evaluate import load_model, resolve_prediction
 
+    if args.consistency and not args.procedural:
+        raise ValueError("--consistency needs --procedural: SRN data carries no geometry to score against")
     if args.backend != "auto":
         ops.set_backend(args.backend)
     dev = torch.device("cuda", 0) if torch.cuda.is_available() else torch.device("cpu")
@@ -134,15 +143,20 @@ def run(args) -> dict:
                 save_png(out[gi * len(w) + i], os.path.join(d, f"{wv:g}.png"))
 
     t1 = time.time()
-    rows, _ = evaluate_objects(model, objects, args.input_view, views, w, args.timesteps, args.batch,
-                               args.autoregressive, args.seed, dev,
-                               on_view=write_pngs if args.save_png else None, solver=args.sampler, eta=args.eta,
-                               spacing=args.spacing, prediction=prediction)
+    rows, _, *rest = evaluate_objects(model, objects, args.input_view, views, w, args.timesteps, args.batch,
+                                      args.autoregressive, args.seed, dev,
+                                      on_view=write_pngs if args.save_png else None, solver=args.sampler,
+                                      eta=args.eta, spacing=args.spacing, prediction=prediction,
+                                      consistency=args.consistency)
     if dev.type == "cuda":
         torch.cuda.synchronize(dev)
     t2 = time.time()
     data = f"procedural seed={args.proc_seed} objects={args.proc_objects}" if args.procedural else args.data
     result = {"args": vars(args), "data": data, "prediction": prediction, "per_image": rows, **summarize(rows)}
+    if args.consistency:
+        from distributed_3d_diffusion_pytorch_amd.engine import gt_ceiling, summarize_consistency
+        result["consistency"] = {"per_w": summarize_consistency(rows, rest[0]), "pairs": rest[0],
+                                 "gt_ceiling": gt_ceiling(objects, args.input_view, views, dev)}
     if args.val_batches > 0:
         result["val_loss"], bins = val_loss(model, cfg, args, dev, prediction)
         if bins is not None:
@@ -157,6 +171,16 @@ def run(args) -> dict:
         p = result["psnr_mean"][k]
         print(f"[evaluate] w={k}: PSNR {'n/a' if p is None else format(p, '.3f')} dB  SSIM "
               f"{result['ssim_mean'][k]:.4f}", flush=True)
+    if args.consistency:
+        fmt = lambda d: "n/a" if d["psnr"] is None else f"{d['psnr']:.3f} dB ({d['n']} px)"  # noqa: E731
+        for k, d in sorted(result["consistency"]["per_w"].items(), key=lambda kv: float(kv[0])):
+            print(f"[evaluate] w={k}: PSNR co-visible {fmt(d['covisible'])}  disoccluded {fmt(d['disoccluded'])}  "
+                  f"background {fmt(d['background'])}", flush=True)
+            print(f"[evaluate] w={k}: reprojection PSNR against the input view {fmt(d['reproj'])}  between generated "
+                  f"views {fmt(d['pairs'])}", flush=True)
+        c = result["consistency"]["gt_ceiling"]
+        print(f"[evaluate] ground-truth ceiling: reprojection PSNR {fmt(c['reproj'])}  pairs {fmt(c['pairs'])}",
+              flush=True)
     print(f"[evaluate] {result['n_images']} images ({result['n_identical']} identical) in "
           f"{result['wall_seconds']:.2f}s -> {os.path.join(args.out, 'metrics.json')}", flush=True)
     return result
