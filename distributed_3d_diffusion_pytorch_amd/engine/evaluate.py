@@ -11,7 +11,10 @@ are scored on the device by ``ops.image_metrics(quantize=True)``, i.e. exactly
 as the PNGs a writer would store.  Objects that carry their geometry (the
 procedural scenes) can also be scored with it: ``ops.view_consistency`` splits
 every generated view into background, disoccluded and co-visible pixels and
-measures how well the views reproject into each other.  Single process.
+measures how well the views reproject into each other.  With ``samples`` > 1
+every (object, guidance weight) runs that many independent chains and
+``ops.ensemble_stats`` scores them as an ensemble: the error of their mean
+image, their spread, and both by visibility class.  Single process.
 """
 from __future__ import annotations
 
@@ -155,7 +158,7 @@ def evaluate_objects(model, objects: Sequence[EvalObject], input_view: int = 0, 
                      autoregressive: bool = False, seed: int = 0, device=None, ref_quirk: bool = False,
                      graph: Optional[bool] = None, keep_images: bool = False,
                      on_view: Optional[Callable] = None, solver: str = "ancestral", eta: float = 0.0,
-                     spacing: str = "t", prediction: str = "eps", consistency: bool = False):
+                     spacing: str = "t", prediction: str = "eps", consistency: bool = False, samples: int = 1):
     """Generate ``views`` of every object from its ``input_view`` and score
     them.  Returns ``(rows, images)``: one row ``{instance, view, w, chain,
     mse, psnr, ssim}`` per (object, view, w) -- ``chain`` the global chain
@@ -178,11 +181,37 @@ def evaluate_objects(model, objects: Sequence[EvalObject], input_view: int = 0, 
     to fp64, what the model was conditioned on.  The function then returns
     ``(rows, images, pair_rows)``: with more than one view, one ``{instance,
     w, chain, src_view, tgt_view, n_clean, mse, psnr}`` per ordered pair of
-    generated views of a chain, the reprojection error of one into the other."""
+    generated views of a chain, the reprojection error of one into the other.
+
+    ``samples`` = C > 1 runs C independent chains per (object, w): chains are
+    object-major, then w, then sample -- chain ``(object * len(w) + i) * C + c``
+    -- so every per-chain row (which gains ``sample`` = c, as the pair rows do),
+    ``images`` ([len(w) * C,3,H,W]) and the batch ``on_view`` sees widen by C,
+    and one sampler step runs ``batch * len(w) * C`` chains.  The function then
+    also returns ``ensemble_rows`` as its last element: per (instance, view, w)
+    the scores of ``ops.ensemble_stats(quantize=True)`` over the C samples --
+    ``samples``, ``n`` (pixels), ``mse_mean_image`` / ``psnr_mean_image`` (the
+    error of the samples' mean image, sum B / (3 n)), ``mse_samples`` (the mean
+    of the samples' errors, sum E / (3 n)), ``spread`` (their variance around
+    the mean image, sum V / (3 n); ``mse_samples = mse_mean_image + spread``),
+    ``psnr_best`` (the best per-chain ``psnr``; None where one is infinite) and
+    ``spread_skill`` = sqrt(V (C + 1) / ((C - 1) B)) (None where B is 0): for
+    samples and truth from one distribution E[B] = (1 + 1/C) sigma^2 and E[V]
+    = (1 - 1/C) sigma^2, so 1 is calibrated and below 1 over-confident.  With
+    ``consistency`` the pixels are split by the class plane of the batch's
+    ``view_consistency`` call (geometry only: the first chain's plane serves
+    all C) and the row gains ``n_<class>``, ``bias_<class>``,
+    ``spread_<class>`` and ``mse_samples_<class>`` for background, disoccluded
+    and covisible (None where the count is 0).  ``samples = 1`` is the path
+    above, chain numbering and return value included."""
     dev = torch.device(device) if device is not None else next(model.parameters()).device
-    nw = len(w)
+    nw, C = len(w), int(samples)
+    if C < 1:
+        raise ValueError(f"samples must be at least 1, got {samples}")
+    nc = nw * C                                    # chains per object
     rows: List[dict] = []
     pair_rows: List[dict] = []
+    ensemble_rows: List[dict] = []
     images: Dict[tuple, torch.Tensor] = {}
     if consistency:
         _scenes(objects)
@@ -190,42 +219,59 @@ def evaluate_objects(model, objects: Sequence[EvalObject], input_view: int = 0, 
         objs = objects[s:s + max(int(batch), 1)]
         G = len(objs)
         # chains are object-major and numbered globally, so a row (and its noise) does not depend on `batch`
-        smp = DiffusionSampler(model, timesteps, ref_quirk, seed=seed, device=dev, chain_offset=s * nw, graph=graph,
+        smp = DiffusionSampler(model, timesteps, ref_quirk, seed=seed, device=dev, chain_offset=s * nc, graph=graph,
                                solver=solver, eta=eta, spacing=spacing, prediction=prediction)
-        group = torch.arange(G).repeat_interleave(nw)
-        wv = torch.tensor([float(x) for x in w]).repeat(G)
+        group = torch.arange(G).repeat_interleave(nc)
+        wv = torch.tensor([float(x) for x in w]).repeat_interleave(C).repeat(G)
         K = torch.stack([o.K for o in objs]).to(dev)
-        records = [[RecordEntry(o.imgs[input_view].to(dev)[None].expand(nw, -1, -1, -1).contiguous(),
+        records = [[RecordEntry(o.imgs[input_view].to(dev)[None].expand(nc, -1, -1, -1).contiguous(),
                                 o.R[input_view].to(dev), o.T[input_view].to(dev))] for o in objs]
         if consistency:
-            table = torch.stack([o.scene for o in objs]).to(dev).double().repeat_interleave(nw, 0)
-            K64 = K.double().repeat_interleave(nw, 0)
-            src = torch.stack([o.imgs[input_view] for o in objs]).to(dev).float().repeat_interleave(nw, 0)
-            sR, sT = _pose64(objs, input_view, dev, nw)
+            table = torch.stack([o.scene for o in objs]).to(dev).double().repeat_interleave(nc, 0)
+            K64 = K.double().repeat_interleave(nc, 0)
+            src = torch.stack([o.imgs[input_view] for o in objs]).to(dev).float().repeat_interleave(nc, 0)
+            sR, sT = _pose64(objs, input_view, dev, nc)
             kept = {}
         for v in views:
             tR = torch.stack([o.R[v] for o in objs]).to(dev)
             tT = torch.stack([o.T[v] for o in objs]).to(dev)
             out = smp.sample_groups(records, tR, tT, K, wv, group).float()
             gt = torch.stack([o.imgs[v] for o in objs]).to(dev)
-            mse, ssim = ops.image_metrics(out, gt.repeat_interleave(nw, 0), quantize=True)
+            mse, ssim = ops.image_metrics(out, gt.repeat_interleave(nc, 0), quantize=True)
             mse_l, ssim_l = mse.double().cpu().tolist(), ssim.double().cpu().tolist()
+            klass = None
             if consistency:
                 kept[int(v)] = out.contiguous()
-                st_l = ops.view_consistency(table, K64, sR, sT, src, *_pose64(objs, v, dev, nw), kept[int(v)],
-                                            gt.float().repeat_interleave(nw, 0)).cpu().tolist()
+                st = ops.view_consistency(table, K64, sR, sT, src, *_pose64(objs, v, dev, nc), kept[int(v)],
+                                          gt.float().repeat_interleave(nc, 0), return_class=C > 1)
+                if C > 1:
+                    st, klass = st[0], st[1][::C].contiguous()
+                st_l = st.cpu().tolist()
+            if C > 1:
+                H, W = out.shape[-2:]
+                es_l = ops.ensemble_stats(out.contiguous().view(G * nw, C, 3, H, W),
+                                          gt.float().repeat_interleave(nw, 0).contiguous(), klass,
+                                          quantize=True).cpu().tolist()
             for gi, o in enumerate(objs):
                 for i in range(nw):
-                    j = gi * nw + i
-                    rows.append({"instance": o.name, "view": int(v), "w": float(w[i]), "chain": s * nw + j,
-                                 "mse": mse_l[j], "psnr": 10.0 * math.log10(1.0 / mse_l[j]) if mse_l[j] > 0 else None,
-                                 "ssim": ssim_l[j]})
-                    if consistency:
-                        rows[-1].update(_consistency_fields(st_l[j]))
+                    for c in range(C):
+                        j = (gi * nw + i) * C + c
+                        rows.append({"instance": o.name, "view": int(v), "w": float(w[i]), "chain": s * nc + j,
+                                     "mse": mse_l[j],
+                                     "psnr": 10.0 * math.log10(1.0 / mse_l[j]) if mse_l[j] > 0 else None,
+                                     "ssim": ssim_l[j]})
+                        if C > 1:
+                            rows[-1]["sample"] = c
+                        if consistency:
+                            rows[-1].update(_consistency_fields(st_l[j]))
+                    if C > 1:
+                        ensemble_rows.append({"instance": o.name, "view": int(v), "w": float(w[i]),
+                                              **_ensemble_fields(es_l[gi * nw + i], C, [r["psnr"] for r in rows[-C:]],
+                                                                 consistency)})
                 if keep_images:
-                    images[(o.name, int(v))] = out[gi * nw:(gi + 1) * nw].cpu()
+                    images[(o.name, int(v))] = out[gi * nc:(gi + 1) * nc].cpu()
                 if autoregressive:
-                    records[gi].append(RecordEntry(out[gi * nw:(gi + 1) * nw].contiguous(), o.R[v].to(dev),
+                    records[gi].append(RecordEntry(out[gi * nc:(gi + 1) * nc].contiguous(), o.R[v].to(dev),
                                                    o.T[v].to(dev)))
             if on_view is not None:
                 on_view(objs, int(v), out, gt)
@@ -234,16 +280,46 @@ def evaluate_objects(model, objects: Sequence[EvalObject], input_view: int = 0, 
                 for vb in kept:
                     if va == vb:
                         continue
-                    st_l = ops.view_consistency(table, K64, *_pose64(objs, va, dev, nw), kept[va],
-                                                *_pose64(objs, vb, dev, nw), kept[vb]).cpu().tolist()
+                    st_l = ops.view_consistency(table, K64, *_pose64(objs, va, dev, nc), kept[va],
+                                                *_pose64(objs, vb, dev, nc), kept[vb]).cpu().tolist()
                     for gi, o in enumerate(objs):
                         for i in range(nw):
-                            j = gi * nw + i
-                            m, p = _ratio(st_l[j][7], st_l[j][3])
-                            pair_rows.append({"instance": o.name, "w": float(w[i]), "chain": s * nw + j,
-                                              "src_view": va, "tgt_view": vb, "n_clean": int(st_l[j][3]), "mse": m,
-                                              "psnr": p})
-    return (rows, images, pair_rows) if consistency else (rows, images)
+                            for c in range(C):
+                                j = (gi * nw + i) * C + c
+                                m, p = _ratio(st_l[j][7], st_l[j][3])
+                                pair_rows.append({"instance": o.name, "w": float(w[i]), "chain": s * nc + j,
+                                                  "src_view": va, "tgt_view": vb, "n_clean": int(st_l[j][3]),
+                                                  "mse": m, "psnr": p})
+                                if C > 1:
+                                    pair_rows[-1]["sample"] = c
+    res = (rows, images, pair_rows) if consistency else (rows, images)
+    return res + (ensemble_rows,) if C > 1 else res
+
+
+def _spread_skill(V: float, B: float, C: int):
+    """sqrt(V (C + 1) / ((C - 1) B)); None where B is 0 (or C is 1)."""
+    if C < 2 or not B > 0:
+        return None
+    return math.sqrt(V * (C + 1) / ((C - 1) * B))
+
+
+def _ensemble_fields(st: Sequence[Sequence[float]], C: int, psnrs: Sequence, by_class: bool) -> dict:
+    """The row fields of one ``ops.ensemble_stats`` [4,4] block; ``psnrs`` the
+    group's per-chain PSNRs."""
+    n, B, V, E = (math.fsum(st[k][j] for k in range(4)) for j in range(4))
+    per = (lambda x: x / (3.0 * n)) if n > 0 else (lambda x: None)  # noqa: E731
+    out = {"samples": C, "n": int(n), "mse_mean_image": per(B),
+           "psnr_mean_image": 10.0 * math.log10(3.0 * n / B) if n > 0 and B > 0 else None,
+           "mse_samples": per(E), "spread": per(V),
+           "psnr_best": None if any(p is None for p in psnrs) else max(psnrs),
+           "spread_skill": _spread_skill(V, B, C)}
+    if by_class:
+        for name, ks in zip(_CLASSES, ((0,), (1,), (2, 3))):
+            nk, Bk, Vk, Ek = (math.fsum(st[k][j] for k in ks) for j in range(4))
+            out[f"n_{name}"] = int(nk)
+            for field, x in ((f"bias_{name}", Bk), (f"spread_{name}", Vk), (f"mse_samples_{name}", Ek)):
+                out[field] = x / (3.0 * nk) if nk > 0 else None
+    return out
 
 
 def _pool(sel: Sequence[dict], count: str, mse: str) -> dict:
@@ -269,6 +345,40 @@ def summarize_consistency(rows: Sequence[dict], pair_rows: Sequence[dict] = ()) 
         d = {name: _pool(sel, f"n_{name}", f"mse_{name}") for name in ("covisible", "disoccluded", "background")}
         d["reproj"] = _pool(sel, "n_clean", "reproj_mse")
         d["pairs"] = _pool([r for r in pair_rows if r["w"] == wv], "n_clean", "mse")
+        out[f"{wv:g}"] = d
+    return out
+
+
+def summarize_ensemble(ensemble_rows: Sequence[dict]) -> dict:
+    """Per guidance weight the pooled scores of ``evaluate_objects(...,
+    samples=C)``: ``{"<w>": {samples, n, mse_mean_image, psnr_mean_image,
+    mse_samples, psnr_samples, spread, spread_skill}}`` and, where the rows
+    carry the classes, ``{name: {n, bias, spread, mse_samples, spread_skill}}``
+    for ``covisible``, ``disoccluded`` and ``background``.  Pooled as
+    :func:`summarize_consistency` pools -- the sum of the rows' sums over the
+    sum of their counts x 3, then the PSNRs and ``spread_skill`` from the
+    pooled sums; None where the count (for a PSNR or the skill: the error) is 0."""
+    def pooled(sel, count, fields):
+        n = sum(int(r[count]) for r in sel)
+        sums = [math.fsum(r[f] * 3.0 * r[count] for r in sel if r[f] is not None) for f in fields]
+        return n, sums
+
+    out = {}
+    for wv in sorted({r["w"] for r in ensemble_rows}):
+        sel = [r for r in ensemble_rows if r["w"] == wv]
+        C = int(sel[0]["samples"])
+        n, (B, V, E) = pooled(sel, "n", ("mse_mean_image", "spread", "mse_samples"))
+        per = (lambda x: x / (3.0 * n)) if n > 0 else (lambda x: None)  # noqa: E731
+        d = {"samples": C, "n": n, "mse_mean_image": per(B), "psnr_mean_image": _ratio(B, n)[1],
+             "mse_samples": per(E), "psnr_samples": _ratio(E, n)[1], "spread": per(V),
+             "spread_skill": _spread_skill(V, B, C)}
+        for name in _CLASSES:
+            if f"n_{name}" not in sel[0]:
+                continue
+            nk, (Bk, Vk, Ek) = pooled(sel, f"n_{name}", (f"bias_{name}", f"spread_{name}", f"mse_samples_{name}"))
+            pk = (lambda x: x / (3.0 * nk)) if nk > 0 else (lambda x: None)  # noqa: E731
+            d[name] = {"n": nk, "bias": pk(Bk), "spread": pk(Vk), "mse_samples": pk(Ek),
+                       "spread_skill": _spread_skill(Vk, Bk, C)}
         out[f"{wv:g}"] = d
     return out
 

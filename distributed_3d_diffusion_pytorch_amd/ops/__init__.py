@@ -277,6 +277,33 @@ def view_consistency(table, K, R_src, t_src, img_src, R_tgt, t_tgt, img_tgt, ref
     return impl.view_consistency(table, K, R_src, t_src, img_src, R_tgt, t_tgt, img_tgt, ref, return_class=return_class)
 
 
+def ensemble_stats(samples, target, klass=None, *, quantize: bool = True, return_maps: bool = False):
+    """Bias, spread and per-sample error of ``samples`` fp32 ``[G,C,3,H,W]`` --
+    C samples of each of G target views -- against ``target`` fp32
+    ``[G,3,H,W]``, both in [-1, 1] and contiguous, per visibility class
+    ``klass`` int32 ``[G,H,W]`` (the class plane of ``view_consistency``: 0
+    background, 1 disoccluded, 2 co-visible, 3 clean; ``None``: every pixel is
+    class 0; a pixel whose class is outside 0..3 enters no row).  Both images
+    are scored on the [0, 1] scale (``quantize``: through the uint8 value
+    ``save_png`` writes, as in ``image_metrics``).  Per pixel, with ``m`` the
+    mean of the C samples: ``B`` = sum over the channels of ``(m - y)^2``,
+    ``V`` = of the population variance of the samples around ``m``, ``E`` = of
+    the mean of ``(x_c - y)^2``; ``E = B + V`` up to rounding.  Returns
+    ``stats`` [G,4,4] fp64, row k = ``[n_k, sum B, sum V, sum E]`` over the
+    pixels of class k (``mse = sum / (3 n)``).  ``return_maps``: also ``mean``
+    [G,3,H,W] fp32 in [-1, 1] (``2 m - 1``) and ``std`` [G,H,W] fp32 on the
+    [0, 1] scale (``sqrt(V / 3)``).  HIP (``csrc/ensemble.hip``, which states
+    the rule) on the GPU, the float64 torch form on the CPU."""
+    G, C, H, W = _t.ensemble_stats_check(samples, target, klass)
+    if G == 0:
+        dev = samples.device
+        stats = torch.zeros(0, _t.ES_CLASSES, _t.ES_COLS, dtype=torch.float64, device=dev)
+        return (stats, torch.zeros(0, 3, H, W, dtype=torch.float32, device=dev),
+                torch.zeros(0, H, W, dtype=torch.float32, device=dev)) if return_maps else stats
+    impl = _h() if samples.is_cuda and use_hip(samples, any_dtype=True) else _t
+    return impl.ensemble_stats(samples, target, klass, quantize=quantize, return_maps=return_maps)
+
+
 def psnr(mse):
     """``10 log10(1 / mse)`` on the [0, 1] scale; ``+inf`` where ``mse == 0``."""
     return -10.0 * torch.log10(torch.as_tensor(mse, dtype=torch.float32))
@@ -288,7 +315,7 @@ posenc_nerf = _t.posenc_nerf
 
 __all__ = ["diffusion_inputs", "diff_loss_nhwc", "diff_loss_rows", "loss_bins_add", "group_norm", "gn_film", "conv3x3", "linear", "film_batch", "cat_gn_silu_dense", "cond_conv", "ray_posenc_dir",
            "ray_origin_pe", "ray_conditioning", "attention", "avgpool2", "upsample2",
-           "silu", "logsnr_mlp", "ray_posenc", "image_metrics", "scene_render", "view_consistency", "psnr", "posenc_ddpm", "camera_rays", "posenc_nerf", "set_backend",
+           "silu", "logsnr_mlp", "ray_posenc", "image_metrics", "scene_render", "view_consistency", "ensemble_stats", "psnr", "posenc_ddpm", "camera_rays", "posenc_nerf", "set_backend",
            "use_hip", "load_library", "library_error", "lib_path"]
 
 

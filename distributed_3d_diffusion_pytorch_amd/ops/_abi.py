@@ -127,6 +127,8 @@ SIGNATURES = {
     "d3d_scene_render": [P, P, P, P, I, I, I, I, I, P, P, P, P],
     # consistency.hip
     "d3d_view_consistency": [P, P, P, P, P, P, P, P, P, I, I, I, I, P, P, P, P],
+    # ensemble.hip
+    "d3d_ensemble_stats": [P, P, P, I, I, I, I, I, P, P, P, P, P],
 }
 
 

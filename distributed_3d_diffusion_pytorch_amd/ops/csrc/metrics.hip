@@ -22,7 +22,7 @@
 // Launch 2 (`image_metrics_final_k`): one wave per image sums that image's
 // partials in a fixed order.  No atomics: image i's result does not depend on
 // N or on the rest of the batch.
-#include "common.h"
+#include "image_map.h"
 
 #define MT_TILE 16
 #define MT_TAPS 11
@@ -32,17 +32,7 @@ struct MetricTaps {
   double g[MT_TAPS];
 };
 
-// [-1, 1] -> [0, 1].  quantize: through the 8-bit value a PNG writer stores,
-// (uint8) trunc((clamp(x) + 1.0f) * 127.5f) with the fp32 add and multiply
-// rounded separately (no FMA), then / 255.
-__device__ __forceinline__ double metric_map01(float x, int quantize) {
-  float c = fminf(fmaxf(x, -1.0f), 1.0f);
-  if (quantize) {
-    float s = __fmul_rn(__fadd_rn(c, 1.0f), 127.5f);
-    return (double)(int)s / 255.0;
-  }
-  return ((double)c + 1.0) * 0.5;
-}
+// (the [-1, 1] -> [0, 1] mapping, metric_map01, is image_map.h)
 
 __global__ __launch_bounds__(256) void image_metrics_tile_k(const float* __restrict__ X, const float* __restrict__ Y,
                                                             int H, int W, int TY, int TX, int quantize,

@@ -2925,3 +2925,23 @@ def view_consistency(table, K, R_src, t_src, img_src, R_tgt, t_tgt, img_tgt, ref
                                        _ptr(ref), N, H, W, _t.SCENE_REF, part.data_ptr(), stats.data_ptr(), _ptr(cls),
                                        _st()), "view_consistency")
     return (stats, cls) if return_class else stats
+
+
+# ------------------------------------------------- multi-sample evaluation ---
+def ensemble_stats(samples, target, klass=None, *, quantize=True, return_maps=False):
+    """stats [G,4,4] fp64 (and, with ``return_maps``, mean [G,3,H,W] fp32 and
+    std [G,H,W] fp32) of the C samples [G,C,3,H,W] of G target views
+    (csrc/ensemble.hip: one thread per pixel, fp64, two passes over the
+    samples, fixed-order block partials and a final sum; the numbers of
+    ``torch_impl.ensemble_stats``).  Graph-capturable."""
+    G, C, H, W = _t.ensemble_stats_check(samples, target, klass)
+    dev = samples.device
+    stats = torch.empty(G, _t.ES_CLASSES, _t.ES_COLS, dtype=torch.float64, device=dev)
+    mean = torch.empty(G, 3, H, W, dtype=F32, device=dev) if return_maps else None
+    std = torch.empty(G, H, W, dtype=F32, device=dev) if return_maps else None
+    if G > 0:
+        part = torch.empty(G * ((H * W + 255) // 256), _t.ES_CLASSES * _t.ES_COLS, dtype=torch.float64, device=dev)
+        _chk(_lib.d3d_ensemble_stats(samples.data_ptr(), target.data_ptr(), _ptr(klass), G, C, H, W,
+                                     int(bool(quantize)), part.data_ptr(), stats.data_ptr(), _ptr(mean), _ptr(std),
+                                     _st()), "ensemble_stats")
+    return (stats, mean, std) if return_maps else stats

@@ -743,3 +743,69 @@ def view_consistency(table, K, R_src, t_src, img_src, R_tgt, t_tgt, img_tgt, ref
     se = ((tg - warp) * 0.5).square().sum(1)
     stats[:, 7] = torch.where(clean, se, zero).flatten(1).sum(1)
     return (stats, klass) if return_class else stats
+
+
+# ------------------------------------------------- multi-sample evaluation ---
+# Ensemble bias, spread and per-sample error of C samples of one target view,
+# per visibility class (csrc/ensemble.hip holds the rule in full).
+ES_CLASSES, ES_COLS = 4, 4
+
+
+def ensemble_stats_check(samples, target, klass=None):
+    """Argument check shared by both backends (ValueError); returns (G, C, H, W)."""
+    name = "ensemble_stats"
+    opt = (("klass", klass),) if klass is not None else ()
+    for nm, x in (("samples", samples), ("target", target)) + opt:
+        if not isinstance(x, torch.Tensor):
+            raise ValueError(f"{name}: {nm} must be a tensor, got {type(x).__name__}")
+        if x.device != samples.device:
+            raise ValueError(f"{name}: {nm} is on {x.device}, the samples on {samples.device}")
+    if samples.dim() != 5 or samples.shape[2] != 3 or min(samples.shape[3:]) < 1:
+        raise ValueError(f"{name}: samples must be [G,C,3,H,W], got {tuple(samples.shape)}")
+    G, C, _, H, W = (int(s) for s in samples.shape)
+    if C < 1:
+        raise ValueError(f"{name}: needs at least one sample per group, got C = {C}")
+    for nm, x, shape, dtype in (("samples", samples, (G, C, 3, H, W), torch.float32),
+                                ("target", target, (G, 3, H, W), torch.float32)) + \
+            ((("klass", klass, (G, H, W), torch.int32),) if klass is not None else ()):
+        if tuple(x.shape) != shape:
+            raise ValueError(f"{name}: {nm} must be {list(shape)} for samples {list(samples.shape)}, got "
+                             f"{tuple(x.shape)}")
+        if x.dtype != dtype:
+            raise ValueError(f"{name}: {nm} must be {str(dtype).replace('torch.', '')}, got {x.dtype}")
+        if not x.is_contiguous():
+            raise ValueError(f"{name}: {nm} must be contiguous")
+    return G, C, H, W
+
+
+def ensemble_stats(samples, target, klass=None, *, quantize=True, return_maps=False):
+    """stats [G,4,4] fp64 -- row k = [n_k, sum B, sum V, sum E] over the pixels
+    of class k -- and, with ``return_maps``, mean [G,3,H,W] fp32 and std
+    [G,H,W] fp32: the float64 torch form of csrc/ensemble.hip, which states the
+    rule, written operation by operation in the kernel's order (the sums over
+    the samples ascending, the channel sums 0, 1, 2)."""
+    G, C, H, W = ensemble_stats_check(samples, target, klass)
+    dt, dev = torch.float64, samples.device
+    x, y = image_map01(samples, quantize), image_map01(target, quantize)
+    s = x[:, 0]
+    for c in range(1, C):
+        s = s + x[:, c]
+    m = s / float(C)                                                    # [G,3,H,W]
+    v, e = torch.zeros_like(m), torch.zeros_like(m)
+    for c in range(C):
+        dv, de = x[:, c] - m, x[:, c] - y
+        v = v + dv * dv
+        e = e + de * de
+    ch = lambda a: (a[:, 0] + a[:, 1]) + a[:, 2]  # noqa: E731
+    db = m - y
+    B, V, E = ch(db * db), ch(v / float(C)), ch(e / float(C))          # [G,H,W]
+    stats = torch.zeros(G, ES_CLASSES, ES_COLS, dtype=dt, device=dev)
+    zero = torch.zeros_like(B)
+    for k in range(ES_CLASSES):
+        mask = (klass == k) if klass is not None else torch.full_like(B, k == 0, dtype=torch.bool)
+        stats[:, k, 0] = mask.flatten(1).sum(1).to(dt)
+        for j, q in enumerate((B, V, E)):
+            stats[:, k, 1 + j] = torch.where(mask, q, zero).flatten(1).sum(1)
+    if return_maps:
+        return stats, (2.0 * m - 1.0).float(), torch.sqrt(V / 3.0).float()
+    return stats

@@ -19,8 +19,13 @@ objects of the ray-cast procedural scenes against their exact renders instead
 of an SRN tree; there ``--consistency`` adds the geometry-aware scores of
 ``ops.view_consistency``: PSNR on the co-visible, disoccluded and background
 pixels, the reprojection error against the input view and between the
-generated views, and the same on the ground truth (``gt_ceiling``).  Single
-process.
+generated views, and the same on the ground truth (``gt_ceiling``).
+``--samples C`` runs C independent chains per (object, guidance weight) -- one
+sampler step then runs ``batch * len(w) * C`` chains -- and adds the ensemble
+scores of ``ops.ensemble_stats``: the error of the samples' mean image, their
+spread and the spread-skill ratio, per visibility class with
+``--consistency``; ``--save_png`` then writes ``<w>_s<c>.png``,
+``mean_<w>.png`` and ``std_<w>.png``.  Single process.
 """
 from __future__ import annotations
 
@@ -52,6 +57,11 @@ def parse(argv=None):
     ap.add_argument("--input_view", type=int, default=0)
     ap.add_argument("--views", default="1,2,3", help="target views (positions in the sorted view list)")
     ap.add_argument("--w", default="3.0", help="guidance weights, one chain per object each")
+    ap.add_argument("--samples", type=int, default=1,
+                    help="independent chains per (object, guidance weight), C >= 1: one sampler step runs "
+                         "batch * len(w) * C chains; with C > 1 metrics.json gets an ensemble block (the error of the "
+                         "samples' mean image, their spread, the spread-skill ratio; per visibility class with "
+                         "--consistency)")
     ap.add_argument("--timesteps", type=int, default=256)
     ap.add_argument("--sampler", default="ancestral", choices=["ancestral", "ddim", "dpmpp2m"],
                     help="update rule: the 256-step ancestral chain, DDIM or DPM-Solver++(2M) for few steps")
@@ -71,7 +81,10 @@ def parse(argv=None):
     ap.add_argument("--out", default="evaluation")
     ap.add_argument("--save_png", action="store_true")
     ap.add_argument("--backend", default="auto")
-    return ap.parse_args(argv)
+    args = ap.parse_args(argv)
+    if args.samples < 1:
+        ap.error(f"--samples must be at least 1, got {args.samples}")
+    return args
 
 
 def val_loss(model, cfg, args, dev, prediction: str):
@@ -132,22 +145,36 @@ def run(args) -> dict:
         raise ValueError(f"no instances in the {args.split} split of {args.data}")
     os.makedirs(args.out, exist_ok=True)
 
+    C = args.samples
+
     def write_pngs(objs, v, out, gt):
         from sampling import save_png
+        if C > 1:                                  # the samples' mean image and their spread, grey min(1, 4 std)
+            _, mean, std = ops.ensemble_stats(out.contiguous().view(len(objs) * len(w), C, *out.shape[1:]),
+                                              gt.float().repeat_interleave(len(w), 0).contiguous(), return_maps=True)
+            mean = mean.cpu().numpy()
+            grey = ((4.0 * std).clamp(max=1.0) * 2.0 - 1.0)[:, None].expand(-1, 3, -1, -1).cpu().numpy()
         out, gt = out.cpu().numpy(), gt.cpu().numpy()
         for gi, o in enumerate(objs):
             d = os.path.join(args.out, o.name, str(v))
             os.makedirs(d, exist_ok=True)
             save_png(gt[gi], os.path.join(d, "gt.png"))
             for i, wv in enumerate(w):
-                save_png(out[gi * len(w) + i], os.path.join(d, f"{wv:g}.png"))
+                j = gi * len(w) + i
+                if C == 1:
+                    save_png(out[j], os.path.join(d, f"{wv:g}.png"))
+                    continue
+                for c in range(C):
+                    save_png(out[j * C + c], os.path.join(d, f"{wv:g}_s{c}.png"))
+                save_png(mean[j], os.path.join(d, f"mean_{wv:g}.png"))
+                save_png(grey[j], os.path.join(d, f"std_{wv:g}.png"))
 
     t1 = time.time()
     rows, _, *rest = evaluate_objects(model, objects, args.input_view, views, w, args.timesteps, args.batch,
                                       args.autoregressive, args.seed, dev,
                                       on_view=write_pngs if args.save_png else None, solver=args.sampler,
                                       eta=args.eta, spacing=args.spacing, prediction=prediction,
-                                      consistency=args.consistency)
+                                      consistency=args.consistency, samples=C)
     if dev.type == "cuda":
         torch.cuda.synchronize(dev)
     t2 = time.time()
@@ -157,6 +184,9 @@ def run(args) -> dict:
         from distributed_3d_diffusion_pytorch_amd.engine import gt_ceiling, summarize_consistency
         result["consistency"] = {"per_w": summarize_consistency(rows, rest[0]), "pairs": rest[0],
                                  "gt_ceiling": gt_ceiling(objects, args.input_view, views, dev)}
+    if C > 1:
+        from distributed_3d_diffusion_pytorch_amd.engine import summarize_ensemble
+        result["ensemble"] = {"per_w": summarize_ensemble(rest[-1]), "rows": rest[-1]}
     if args.val_batches > 0:
         result["val_loss"], bins = val_loss(model, cfg, args, dev, prediction)
         if bins is not None:
@@ -181,6 +211,17 @@ def run(args) -> dict:
         c = result["consistency"]["gt_ceiling"]
         print(f"[evaluate] ground-truth ceiling: reprojection PSNR {fmt(c['reproj'])}  pairs {fmt(c['pairs'])}",
               flush=True)
+    if C > 1:
+        db = lambda x: "n/a" if x is None else f"{x:.3f} dB"  # noqa: E731
+        num = lambda x, f: "n/a" if x is None else format(x, f)  # noqa: E731
+        for k, d in sorted(result["ensemble"]["per_w"].items(), key=lambda kv: float(kv[0])):
+            print(f"[evaluate] w={k}: {C} samples: PSNR of the mean image {db(d['psnr_mean_image'])}  of the samples "
+                  f"{db(d['psnr_samples'])}  spread {num(d['spread'], '.3e')}  spread-skill "
+                  f"{num(d['spread_skill'], '.3f')}", flush=True)
+            if args.consistency:
+                print(f"[evaluate] w={k}: spread co-visible {num(d['covisible']['spread'], '.3e')}  disoccluded "
+                      f"{num(d['disoccluded']['spread'], '.3e')}  background "
+                      f"{num(d['background']['spread'], '.3e')}", flush=True)
     print(f"[evaluate] {result['n_images']} images ({result['n_identical']} identical) in "
           f"{result['wall_seconds']:.2f}s -> {os.path.join(args.out, 'metrics.json')}", flush=True)
     return result
