@@ -107,6 +107,10 @@ SIGNATURES = {
     "d3d_gemm_nt_gn": [P, P, P, P, P, I, I, I, I, I, I, I, F, F, P, I, I, P],
     "d3d_attn_bwd": [P, P, P, P, P, P, I, I, I, I, I, F, P],
     "d3d_attn_bwd_slabs": [I, I, I, I],
+    # attention_hd.hip (head dims 32 and 256)
+    "d3d_attn_hd_fwd": [P, P, P, I, I, I, I, I, F, P],
+    "d3d_attn_hd_bwd": [P, P, P, P, P, P, I, I, I, I, I, F, P],
+    "d3d_attn_hd_bwd_slabs": [I, I, I, I],
     # wgrad_group.hip (job tables: arrays of hip_impl._WgJob)
     "d3d_wgrad_group_cfg": [I, I, I],
     "d3d_wgrad_group_ok": [P],

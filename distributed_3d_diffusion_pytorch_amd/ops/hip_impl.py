@@ -2282,13 +2282,50 @@ class _Attention(torch.autograd.Function):
         return dqkv, None, None
 
 
+class _AttentionHD(torch.autograd.Function):
+    """Head dims 32 (head-pair kernels) and 256 (split-D kernels): attention_hd.hip."""
+
+    @staticmethod
+    def forward(ctx, qkv, heads, cross):
+        qkv = qkv.contiguous()
+        N, L, C3 = qkv.shape
+        C = C3 // 3
+        out = torch.empty(N, L, C, dtype=BF16, device=qkv.device)
+        lse = torch.empty(N, heads, L, dtype=F32, device=qkv.device)
+        scale = 1.0 / math.sqrt(C // heads)
+        _chk(_lib.d3d_attn_hd_fwd(qkv.data_ptr(), out.data_ptr(), lse.data_ptr(), N, L, C, heads, int(cross), scale,
+                                  _st()), "attn_hd_fwd")
+        ctx.save_for_backward(qkv, out, lse)
+        ctx.cfg = (heads, cross, scale)
+        return out
+
+    @staticmethod
+    def backward(ctx, dout):
+        qkv, out, lse = ctx.saved_tensors
+        heads, cross, scale = ctx.cfg
+        N, L, C3 = qkv.shape
+        C = C3 // 3
+        dout = dout.contiguous()
+        # dQ is written directly while one workgroup owns every key (L <= 256
+        # at head dim 32, L <= 64 at head dim 256); longer sequences take one
+        # fp32 slab per 64-key block, summed in fixed order
+        slabs = _lib.d3d_attn_hd_bwd_slabs(N, L, C, heads)
+        dq = torch.empty(slabs, N, L, C, dtype=F32, device=qkv.device) if slabs else None
+        dqkv = torch.empty_like(qkv)
+        _chk(_lib.d3d_attn_hd_bwd(qkv.data_ptr(), out.data_ptr(), dout.data_ptr(), lse.data_ptr(), _ptr(dq),
+                                  dqkv.data_ptr(), N, L, C, heads, int(cross), scale, _st()), "attn_hd_bwd")
+        return dqkv, None, None
+
+
 def attention(qkv, heads, cross):
     _need_bf16(qkv)
     N, L, C3 = qkv.shape
     D = C3 // 3 // heads
-    if D not in (64, 128) or (cross and N % 2):
+    if D not in (32, 64, 128, 256) or (cross and N % 2):
         _fallback("attention", f"L={L} head_dim={D} N={N} cross={cross}")
         return _t.attention(qkv, heads, cross)
+    if D in (32, 256):
+        return _AttentionHD.apply(qkv, heads, cross)
     return _Attention.apply(qkv, heads, cross)
 
 

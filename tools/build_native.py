@@ -23,6 +23,9 @@ SRC = os.path.join(PKG, "ops", "csrc")
 OUT = os.path.join(PKG, "ops", "libd3d_hip.so")
 OBJ = os.path.join(ROOT, "build", "native")
 ARCH = os.environ.get("D3D_OFFLOAD_ARCH", "gfx950")
+# Flags of single translation units.  attention_hd.hip: scalar fp32 VALU only
+# (no packed fp32 add / mul / fma forms in the accumulator rescales).
+FILE_FLAGS = {"attention_hd.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]}
 
 
 def hipcc() -> str:
@@ -64,7 +67,7 @@ def build(force: bool = False, jobs: int = 8, debug: bool = False, verbose: bool
         obj = os.path.join(OBJ_, os.path.basename(src)[:-4] + ".o")
         if not force and os.path.exists(obj) and os.path.getmtime(obj) >= dep_mtime(src):
             return obj
-        cmd = [cc, *flags, "-c", src, "-o", obj]
+        cmd = [cc, *flags, *FILE_FLAGS.get(os.path.basename(src), []), "-c", src, "-o", obj]
         r = subprocess.run(cmd, capture_output=True, text=True)
         if r.returncode != 0:
             raise RuntimeError(f"compile failed: {' '.join(cmd)}\n{r.stderr}")
