@@ -1,0 +1,132 @@
+"""Radiance-field consistency: 3DiM's "3D consistency scoring".
+
+The views a sampler generated for one object are split into training and
+held-out views; a dense voxel radiance field is fitted to the training views
+(``ops.field_loss_grad``, one fused kernel pass per iteration, Adam on the
+grid) and its renders of the held-out poses (``ops.field_render``) are scored
+against the held-out generated views with ``ops.image_metrics``.  Views that
+agree with one 3D object score high; views that each look plausible but
+disagree score low.  Only the poses are needed, no geometry, so the score
+exists for SRN data as well as for the procedural scenes.  Single process.
+"""
+from __future__ import annotations
+
+import math
+from typing import Dict, List, Sequence
+
+import torch
+
+from .. import ops
+from ..ops.torch_impl import hash_u32
+
+# Chosen on procedural ground-truth views at 64 x 64 (profiles/field/README.md holds the sweep).
+FIT_ITERS, FIT_RAYS, FIT_LR = 300, 4096, 0.1
+
+
+def _rays(R, t, K, H: int, W: int, rescale_from: int):
+    """(o, d) fp32 [V * H * W, 3] of V cameras, in image order."""
+    pos, dirs = ops.camera_rays(R[None], t[None], K[None], H, W, rescale_from)
+    return pos.reshape(-1, 3).contiguous(), dirs.reshape(-1, 3).contiguous()
+
+
+def fit_field(images, R, t, K, *, grid: int = 48, samples: int = 64, bound: float = 1.0, iters: int = FIT_ITERS,
+              rays_per_iter: int = FIT_RAYS, lr: float = FIT_LR, seed: int = 0, rescale_from: int = 128):
+    """Fit a voxel radiance field ``[grid,grid,grid,4]`` (the layout of
+    ``ops.field_render``) to ``images`` [V,3,H,W] in [-1, 1] seen by the
+    cameras ``R`` [V,3,3] cam-to-world, ``t`` [V,3] and ``K`` [3,3] (the
+    intrinsics of the ``rescale_from``-pixel image, as ``ops.camera_rays``
+    takes them; 0: of this size).  Iteration i draws ``rays_per_iter`` of the V
+    H W rays, with replacement, by the counter hash of ``(seed, i)`` and takes
+    one Adam step of rate ``lr`` on the mean squared error of
+    ``ops.field_loss_grad`` from a zero grid, so a fit is a pure function of its
+    arguments on a given backend.  Returns ``(grid, history)``: ``history``
+    fp64 [iters] on the images' device, the per-iteration mean loss (over rays
+    and channels)."""
+    if images.dim() != 4 or images.shape[1] != 3:
+        raise ValueError(f"fit_field: images must be [V,3,H,W], got {tuple(images.shape)}")
+    V, _, H, W = (int(s) for s in images.shape)
+    if tuple(R.shape) != (V, 3, 3) or tuple(t.shape) != (V, 3) or tuple(K.shape) != (3, 3):
+        raise ValueError(f"fit_field: R, t, K must be [{V},3,3], [{V},3], [3,3], got {tuple(R.shape)}, "
+                         f"{tuple(t.shape)}, {tuple(K.shape)}")
+    if iters < 1 or rays_per_iter < 1:
+        raise ValueError(f"fit_field: iters and rays_per_iter must be at least 1, got {iters} and {rays_per_iter}")
+    dev = images.device
+    o, d = _rays(R.to(dev), t.to(dev), K.to(dev), H, W, rescale_from)
+    y = images.float().permute(0, 2, 3, 1).reshape(-1, 3).contiguous()
+    N, n = V * H * W, int(rays_per_iter)
+    g = torch.zeros(grid, grid, grid, 4, dtype=torch.float32, device=dev)
+    opt = torch.optim.Adam([g], lr=lr)
+    history = torch.zeros(iters, dtype=torch.float64, device=dev)
+    lane = torch.arange(n, dtype=torch.int64, device=dev)
+    for it in range(iters):
+        # sorted: neighbouring lanes of the kernel then hold neighbouring pixels of one view
+        idx = torch.sort(hash_u32(seed, lane + it * n) % N).values
+        loss, grad = ops.field_loss_grad(g, o[idx], d[idx], y[idx], samples=samples, bound=bound)
+        g.grad = grad / (3.0 * n)
+        opt.step()
+        history[it] = loss / (3.0 * n)
+    return g.detach(), history
+
+
+def field_consistency(images, R, t, K, train: Sequence[int], test: Sequence[int], **fit) -> dict:
+    """The score of one set of views: fit a field (:func:`fit_field`, ``fit``
+    its keywords) to ``images[train]``, render the poses of ``test`` and score
+    the renders against ``images[test]`` with ``ops.image_metrics`` (as 8-bit
+    PNGs).  Returns ``field_psnr`` / ``field_ssim`` (the means over the test
+    views; a view rendered exactly counts with 100 dB), ``field_psnr_views`` /
+    ``field_ssim_views``, ``fit_loss`` (the last iteration's mean loss) and
+    ``n_train`` / ``n_test``.  Fewer than 3 training views, or no test view,
+    is a ValueError."""
+    train, test = [int(v) for v in train], [int(v) for v in test]
+    if len(train) < 3:
+        raise ValueError(f"field_consistency needs at least 3 training views, got {len(train)}")
+    if not test:
+        raise ValueError("field_consistency needs at least one held-out view")
+    H, W = (int(s) for s in images.shape[-2:])
+    dev = images.device
+    grid, history = fit_field(images[train], R[train], t[train], K, **fit)
+    o, d = _rays(R[test].to(dev), t[test].to(dev), K.to(dev), H, W, fit.get("rescale_from", 128))
+    C = ops.field_render(grid, o, d, samples=fit.get("samples", 64), bound=fit.get("bound", 1.0), width=W)
+    pred = (C.view(len(test), H, W, 3).permute(0, 3, 1, 2) * 2.0 - 1.0).contiguous()
+    mse, ssim = ops.image_metrics(pred, images[test].float().contiguous(), quantize=True)
+    psnr = [10.0 * math.log10(1.0 / m) if m > 0 else 100.0 for m in mse.double().cpu().tolist()]
+    ssim = ssim.double().cpu().tolist()
+    return {"field_psnr": sum(psnr) / len(psnr), "field_ssim": sum(ssim) / len(ssim), "field_psnr_views": psnr,
+            "field_ssim_views": ssim, "fit_loss": float(history[-1]), "n_train": len(train), "n_test": len(test)}
+
+
+def field_rows(objects, images: Dict[tuple, torch.Tensor], views: Sequence[int], holdout: Sequence[int],
+               w: Sequence[float], device=None, **fit) -> List[dict]:
+    """One :func:`field_consistency` row per (object, guidance weight) of an
+    ``evaluate_objects(..., keep_images=True)`` run: ``images[(instance, view)]``
+    the generated ``[len(w),3,H,W]`` batch; the views in ``holdout`` are held
+    out, the other generated views are the training set.  ``images`` None:
+    the objects' own (ground-truth) images, one row per object with ``w``
+    None -- the ceiling of the score at this grid and view count."""
+    views, holdout = [int(v) for v in views], [int(v) for v in holdout]
+    bad = [v for v in holdout if v not in views]
+    if bad or len(set(holdout)) != len(holdout):
+        raise ValueError(f"the held-out views must be distinct views of {views}, got {holdout}")
+    train = [i for i, v in enumerate(views) if v not in holdout]
+    test = [i for i, v in enumerate(views) if v in holdout]
+    dev = torch.device(device) if device is not None else torch.device("cpu")
+    rows = []
+    for o in objects:
+        R = torch.stack([o.R[v] for v in views]).to(dev)
+        t = torch.stack([o.T[v] for v in views]).to(dev)
+        for i, wv in enumerate(w if images is not None else (None,)):
+            img = torch.stack([o.imgs[v] if images is None else images[(o.name, v)][i] for v in views]).to(dev)
+            rows.append({"instance": o.name, "w": None if wv is None else float(wv),
+                         **field_consistency(img.float(), R, t, o.K.to(dev), train, test, **fit)})
+    return rows
+
+
+def summarize_field(rows: Sequence[dict]) -> dict:
+    """Per guidance weight (``"gt"`` for the ground-truth rows) the means of
+    ``field_psnr``, ``field_ssim`` and ``fit_loss`` over the objects."""
+    out = {}
+    for wv in sorted({r["w"] for r in rows}, key=lambda x: -math.inf if x is None else x):
+        sel = [r for r in rows if r["w"] == wv]
+        out["gt" if wv is None else f"{wv:g}"] = {"n": len(sel), **{k: sum(r[k] for r in sel) / len(sel)
+                                                                  for k in ("field_psnr", "field_ssim", "fit_loss")}}
+    return out

@@ -304,6 +304,42 @@ def ensemble_stats(samples, target, klass=None, *, quantize: bool = True, return
     return impl.ensemble_stats(samples, target, klass, quantize=quantize, return_maps=return_maps)
 
 
+def field_render(grid, rays_o, rays_d, *, samples: int, bound: float = 1.0, width: int = 0):
+    """Colours ``[R,3]`` fp32 on the [0, 1] scale of R rays through a dense
+    voxel radiance field: ``grid`` fp32 ``[G,G,G,4]``, contiguous, indexed
+    ``[iz,iy,ix,c]`` with channels (raw_r, raw_g, raw_b, raw_sigma) over the
+    cube ``[-bound, bound]^3``; ``rays_o``, ``rays_d`` fp32 ``[R,3]``, the
+    directions of unit length.  ``samples`` equal steps through the cube,
+    trilinear reads, softplus density, sigmoid colour, a white background
+    (``csrc/field.hip`` states the rule in full).  ``width``: the rays are the
+    pixels of images of that width in row order (it divides R), which lets a
+    wave of the kernel take an 8 x 8 pixel tile; the result does not depend on
+    it.  Forward only.  HIP on the GPU, the float64 torch form on the CPU."""
+    _, R = _t.field_check("field_render", grid, rays_o, rays_d, samples=samples, bound=bound, width=width)
+    if R == 0:
+        return torch.zeros(0, 3, dtype=torch.float32, device=grid.device)
+    impl = _h() if grid.is_cuda and use_hip(grid, any_dtype=True) else _t
+    return impl.field_render(grid, rays_o, rays_d, samples=samples, bound=bound, width=width)
+
+
+def field_loss_grad(grid, rays_o, rays_d, target, *, samples: int, bound: float = 1.0, width: int = 0):
+    """``(loss, grad)`` of one iteration of a field fit: ``loss`` the fp64
+    scalar ``sum_rays sum_ch (C - (target + 1) / 2)^2`` of the colours ``C`` of
+    :func:`field_render` against ``target`` fp32 ``[R,3]`` in [-1, 1] (a sum:
+    the caller divides), ``grad`` fp32 ``[G,G,G,4]`` its gradient on ``grid``.
+    No autograd: the op is the fused forward and backward.  Both outputs are
+    bitwise reproducible; ``grad`` does not depend on the order of the rays.
+    ``R * samples`` beyond the gradient's fixed-point range (about 1.4 million
+    at ``bound = 1``) is a ValueError: split the rays.  HIP
+    (``csrc/field.hip``) on the GPU, the float64 torch form on the CPU."""
+    G, R = _t.field_check("field_loss_grad", grid, rays_o, rays_d, target, samples=samples, bound=bound, width=width)
+    if R == 0:
+        return (torch.zeros((), dtype=torch.float64, device=grid.device),
+                torch.zeros(G, G, G, 4, dtype=torch.float32, device=grid.device))
+    impl = _h() if grid.is_cuda and use_hip(grid, any_dtype=True) else _t
+    return impl.field_loss_grad(grid, rays_o, rays_d, target, samples=samples, bound=bound, width=width)
+
+
 def psnr(mse):
     """``10 log10(1 / mse)`` on the [0, 1] scale; ``+inf`` where ``mse == 0``."""
     return -10.0 * torch.log10(torch.as_tensor(mse, dtype=torch.float32))
@@ -315,7 +351,7 @@ posenc_nerf = _t.posenc_nerf
 
 __all__ = ["diffusion_inputs", "diff_loss_nhwc", "diff_loss_rows", "loss_bins_add", "group_norm", "gn_film", "conv3x3", "linear", "film_batch", "cat_gn_silu_dense", "cond_conv", "ray_posenc_dir",
            "ray_origin_pe", "ray_conditioning", "attention", "avgpool2", "upsample2",
-           "silu", "logsnr_mlp", "ray_posenc", "image_metrics", "scene_render", "view_consistency", "ensemble_stats", "psnr", "posenc_ddpm", "camera_rays", "posenc_nerf", "set_backend",
+           "silu", "logsnr_mlp", "ray_posenc", "image_metrics", "scene_render", "view_consistency", "ensemble_stats", "field_render", "field_loss_grad", "psnr", "posenc_ddpm", "camera_rays", "posenc_nerf", "set_backend",
            "use_hip", "load_library", "library_error", "lib_path"]
 
 

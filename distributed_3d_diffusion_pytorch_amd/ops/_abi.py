@@ -133,6 +133,10 @@ SIGNATURES = {
     "d3d_view_consistency": [P, P, P, P, P, P, P, P, P, I, I, I, I, P, P, P, P],
     # ensemble.hip
     "d3d_ensemble_stats": [P, P, P, I, I, I, I, I, P, P, P, P, P],
+    # field.hip
+    "d3d_field_blocks": [I, I],
+    "d3d_field_render": [P, P, P, P, I, I, I, C.c_double, I, P],
+    "d3d_field_loss_grad": [P, P, P, P, P, P, P, P, I, I, I, C.c_double, I, P],
 }
 
 

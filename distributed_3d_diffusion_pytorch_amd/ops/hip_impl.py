@@ -2982,3 +2982,45 @@ def ensemble_stats(samples, target, klass=None, *, quantize=True, return_maps=Fa
                                      int(bool(quantize)), part.data_ptr(), stats.data_ptr(), _ptr(mean), _ptr(std),
                                      _st()), "ensemble_stats")
     return (stats, mean, std) if return_maps else stats
+
+
+# ------------------------------------------------ radiance-field consistency ---
+# The gradient's fixed-point accumulators, int64 [G^3 4] per (device, G): zero
+# between calls (field_convert_k clears what it converts).
+_FIELD_ACC: Dict[tuple, torch.Tensor] = {}
+
+
+def field_render(grid, rays_o, rays_d, *, samples, bound=1.0, width=0):
+    """C [R,3] fp32 on the [0, 1] scale of R rays through the voxel field
+    ``grid`` [G,G,G,4] (csrc/field.hip: one thread per ray, one walk in
+    registers; ``width``: the rays are image rows of that width and a wave
+    takes an 8 x 8 pixel tile).  Graph-capturable."""
+    G, R = _t.field_check("field_render", grid, rays_o, rays_d, samples=samples, bound=bound, width=width)
+    out = torch.empty(R, 3, dtype=F32, device=grid.device)
+    if R > 0:
+        _chk(_lib.d3d_field_render(grid.data_ptr(), rays_o.data_ptr(), rays_d.data_ptr(), out.data_ptr(), R,
+                                   int(samples), G, float(bound), int(width), _st()), "field_render")
+    return out
+
+
+def field_loss_grad(grid, rays_o, rays_d, target, *, samples, bound=1.0, width=0):
+    """(L fp64 scalar, dL/dgrid fp32 [G,G,G,4]) of R rays against ``target``
+    [R,3] (csrc/field.hip: two forward walks per ray in registers, the
+    gradient through 64-bit fixed-point integer atomics, the loss through
+    fixed-order block partials; bitwise reproducible)."""
+    G, R = _t.field_check("field_loss_grad", grid, rays_o, rays_d, target, samples=samples, bound=bound, width=width)
+    dev = grid.device
+    loss = torch.zeros((), dtype=torch.float64, device=dev)
+    grad = torch.empty(G, G, G, 4, dtype=F32, device=dev)
+    if R == 0:
+        return loss, grad.zero_()
+    key = (dev, G)
+    acc = _FIELD_ACC.pop(key, None)
+    if acc is None:
+        acc = torch.zeros(G * G * G * 4, dtype=torch.int64, device=dev)
+    part = torch.empty(_lib.d3d_field_blocks(R, int(width)), dtype=torch.float64, device=dev)
+    _chk(_lib.d3d_field_loss_grad(grid.data_ptr(), rays_o.data_ptr(), rays_d.data_ptr(), target.data_ptr(),
+                                  acc.data_ptr(), part.data_ptr(), loss.data_ptr(), grad.data_ptr(), R, int(samples),
+                                  G, float(bound), int(width), _st()), "field_loss_grad")
+    _FIELD_ACC[key] = acc                          # (a failed launch drops it: its contents are unknown)
+    return loss, grad

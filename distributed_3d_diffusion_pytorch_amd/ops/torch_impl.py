@@ -809,3 +809,119 @@ def ensemble_stats(samples, target, klass=None, *, quantize=True, return_maps=Fa
     if return_maps:
         return stats, (2.0 * m - 1.0).float(), torch.sqrt(V / 3.0).float()
     return stats
+
+
+# ------------------------------------------------ radiance-field consistency ---
+# A dense voxel radiance field rendered by fixed-step quadrature, its squared
+# error against target colours and the gradient on the grid (csrc/field.hip
+# holds the rule in full).
+FIELD_FIX_BITS = 36                  # the gradient's fixed-point scale, 2^36 (csrc/field.hip)
+FIELD_FIX_BUDGET = float(1 << 23)    # R S M <= 2^23: 8 R S M 2^36 <= 2^62 < 2^63
+FIELD_T_MAX = 3.0e38                 # the far end before the first slab (finite: no inf arithmetic)
+
+
+def field_fix_load(R: int, samples: int, bound: float) -> float:
+    """``R S M`` of the fixed-point bound: ``M = 6 max(1, delta_max)`` bounds
+    one contribution (``|dL/dC| <= 2`` on 3 channels, ``|dC/dsigma| <=
+    delta``), ``delta_max = 2 sqrt(3) bound / S`` the longest chord's step."""
+    return float(R) * samples * 6.0 * max(1.0, 2.0 * math.sqrt(3.0) * bound / samples)
+
+
+def field_check(name, grid, rays_o, rays_d, target=None, *, samples, bound, width=0):
+    """Argument check shared by both backends (ValueError); returns (G, R)."""
+    opt = (("target", target),) if target is not None else ()
+    for nm, x in (("grid", grid), ("rays_o", rays_o), ("rays_d", rays_d)) + opt:
+        if not isinstance(x, torch.Tensor):
+            raise ValueError(f"{name}: {nm} must be a tensor, got {type(x).__name__}")
+        if x.device != grid.device:
+            raise ValueError(f"{name}: {nm} is on {x.device}, the grid on {grid.device}")
+        if x.dtype != torch.float32:
+            raise ValueError(f"{name}: {nm} must be float32, got {x.dtype}")
+        if not x.is_contiguous():
+            raise ValueError(f"{name}: {nm} must be contiguous")
+    if grid.dim() != 4 or grid.shape[3] != 4 or not grid.shape[0] == grid.shape[1] == grid.shape[2]:
+        raise ValueError(f"{name}: grid must be [G,G,G,4], got {tuple(grid.shape)}")
+    G = int(grid.shape[0])
+    if G < 2:
+        raise ValueError(f"{name}: the grid needs at least 2 nodes per axis, got G = {G}")
+    if rays_o.dim() != 2 or rays_o.shape[1] != 3:
+        raise ValueError(f"{name}: rays_o must be [R,3], got {tuple(rays_o.shape)}")
+    R = int(rays_o.shape[0])
+    for nm, x in (("rays_d", rays_d),) + opt:
+        if tuple(x.shape) != (R, 3):
+            raise ValueError(f"{name}: {nm} must be [{R}, 3] as rays_o, got {tuple(x.shape)}")
+    if isinstance(samples, bool) or not isinstance(samples, int) or samples < 1:
+        raise ValueError(f"{name}: samples must be an integer >= 1, got {samples!r}")
+    if not (isinstance(bound, (int, float)) and 0.0 < float(bound) < float("inf")):
+        raise ValueError(f"{name}: bound must be a positive finite number, got {bound!r}")
+    if isinstance(width, bool) or not isinstance(width, int) or width < 0 or (width > 0 and R % width != 0):
+        raise ValueError(f"{name}: width must be 0 or an image width that divides R = {R}, got {width!r}")
+    if target is not None and field_fix_load(R, samples, float(bound)) > FIELD_FIX_BUDGET:
+        raise ValueError(f"{name}: R * samples = {R * samples} is beyond the gradient's fixed-point range "
+                         f"(R S 6 max(1, 2 sqrt(3) bound / S) <= 2^23); split the rays over several calls")
+    return G, R
+
+
+def _field_march(grid, o, d, S: int, bound: float, dt):
+    """C [R,3] on the [0, 1] scale of csrc/field.hip's rule, in ``dt``."""
+    G = grid.shape[0]
+    o, d, flat = o.to(dt), d.to(dt), grid.reshape(-1, 4)
+    b = torch.tensor(bound, dtype=dt, device=o.device)
+    t0 = torch.zeros_like(o[:, 0])
+    t1 = torch.full_like(t0, FIELD_T_MAX)
+    hit = torch.ones_like(t0, dtype=torch.bool)
+    for a in range(3):
+        zero = d[:, a] == 0
+        da = torch.where(zero, torch.ones_like(t0), d[:, a])
+        ta, tb = (-b - o[:, a]) / da, (b - o[:, a]) / da
+        t0 = torch.where(zero, t0, torch.maximum(t0, torch.minimum(ta, tb)))
+        t1 = torch.where(zero, t1, torch.minimum(t1, torch.maximum(ta, tb)))
+        hit = hit & (~zero | (o[:, a].abs() <= b))
+    hit = hit & (t1 > t0)
+    t0 = torch.where(hit, t0, torch.zeros_like(t0))
+    delta = torch.where(hit, (t1 - t0) / S, torch.zeros_like(t0))
+    ti = t0[:, None] + (torch.arange(S, dtype=dt, device=o.device) + 0.5) * delta[:, None]      # [R,S]
+    pos = o[:, None, :] + ti[..., None] * d[:, None, :]                                          # [R,S,3]
+    g = ((pos + b) * torch.tensor((G - 1) / (2.0 * bound), dtype=dt, device=o.device)).clamp(0, G - 1)
+    i0 = g.detach().floor().clamp(max=G - 2).long()
+    f = g - i0.to(dt)
+    v = torch.zeros(*ti.shape, 4, dtype=dt, device=o.device)
+    for k in range(8):                     # corner k = (dz, dy, dx), ascending: the kernel's order
+        dz, dy, dx = k >> 2, (k >> 1) & 1, k & 1
+        wx = f[..., 0] if dx else 1 - f[..., 0]
+        wy = f[..., 1] if dy else 1 - f[..., 1]
+        wz = f[..., 2] if dz else 1 - f[..., 2]
+        idx = ((i0[..., 2] + dz) * G + (i0[..., 1] + dy)) * G + (i0[..., 0] + dx)
+        v = v + ((wz * wy) * wx)[..., None] * flat[idx]
+    raw = v[..., 3]
+    sigma = raw.clamp(min=0) + torch.log1p(torch.exp(-raw.abs()))
+    rgb = torch.sigmoid(v[..., :3])
+    alpha = -torch.expm1(-sigma * delta[:, None])
+    T = torch.ones_like(t0)
+    C = torch.zeros_like(o)
+    for i in range(S):
+        C = C + (T * alpha[:, i])[:, None] * rgb[:, i]
+        T = T * (1 - alpha[:, i])
+    C = C + T[:, None]
+    return torch.where(hit[:, None], C, torch.ones_like(C))
+
+
+def field_render(grid, rays_o, rays_d, *, samples, bound=1.0, width=0, dtype=torch.float64):
+    """C [R,3] fp32 on the [0, 1] scale: the float64 torch form of
+    csrc/field.hip (``dtype``: the precision it is evaluated in)."""
+    field_check("field_render", grid, rays_o, rays_d, samples=samples, bound=bound, width=width)
+    with torch.no_grad():
+        return _field_march(grid.to(dtype), rays_o, rays_d, samples, float(bound), dtype).float()
+
+
+def field_loss_grad(grid, rays_o, rays_d, target, *, samples, bound=1.0, width=0, dtype=torch.float64):
+    """(L fp64 scalar, dL/dgrid fp32 [G,G,G,4]): the float64 torch form of
+    csrc/field.hip, the gradient by autograd over the composition, rounded to
+    fp32 at the end (``dtype``: the precision it is evaluated in)."""
+    field_check("field_loss_grad", grid, rays_o, rays_d, target, samples=samples, bound=bound, width=width)
+    with torch.enable_grad():
+        g = grid.detach().to(dtype).requires_grad_(True)
+        C = _field_march(g, rays_o, rays_d, samples, float(bound), dtype)
+        L = (C - (target.to(dtype) + 1) * 0.5).square().sum()
+        grad, = torch.autograd.grad(L, g)
+    return L.detach().double(), grad.float()

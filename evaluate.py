@@ -25,7 +25,13 @@ sampler step then runs ``batch * len(w) * C`` chains -- and adds the ensemble
 scores of ``ops.ensemble_stats``: the error of the samples' mean image, their
 spread and the spread-skill ratio, per visibility class with
 ``--consistency``; ``--save_png`` then writes ``<w>_s<c>.png``,
-``mean_<w>.png`` and ``std_<w>.png``.  Single process.
+``mean_<w>.png`` and ``std_<w>.png``.  ``--field_holdout a,b`` adds 3DiM's 3D
+consistency score (``engine.field_consistency``): per (object, guidance
+weight) a voxel radiance field is fitted to the generated ``--views`` that are
+not held out and its renders are scored against the held-out generated views;
+it needs only the poses, so it works on SRN data, and with ``--procedural``
+the same score of the ground-truth images (``gt_field``) gives its ceiling.
+Single process.
 """
 from __future__ import annotations
 
@@ -62,6 +68,12 @@ def parse(argv=None):
                          "batch * len(w) * C chains; with C > 1 metrics.json gets an ensemble block (the error of the "
                          "samples' mean image, their spread, the spread-skill ratio; per visibility class with "
                          "--consistency)")
+    ap.add_argument("--field_holdout", default="",
+                    help="views of --views to hold out for the radiance-field consistency score: a field is fitted "
+                         "to the other generated views (at least 3) of each (object, w) and its renders are scored "
+                         "against the held-out generated views; metrics.json gets a field block")
+    ap.add_argument("--field_grid", type=int, default=48, help="--field_holdout: nodes per axis of the field")
+    ap.add_argument("--field_iters", type=int, default=0, help="--field_holdout: fit iterations (0 = the default)")
     ap.add_argument("--timesteps", type=int, default=256)
     ap.add_argument("--sampler", default="ancestral", choices=["ancestral", "ddim", "dpmpp2m"],
                     help="update rule: the 256-step ancestral chain, DDIM or DPM-Solver++(2M) for few steps")
@@ -84,6 +96,16 @@ def parse(argv=None):
     args = ap.parse_args(argv)
     if args.samples < 1:
         ap.error(f"--samples must be at least 1, got {args.samples}")
+    if args.field_holdout:
+        views = [int(v) for v in args.views.split(",")]
+        hold = [int(v) for v in args.field_holdout.split(",")]
+        if args.samples > 1:
+            ap.error("--field_holdout together with --samples C > 1 is not supported")
+        if len(set(hold)) != len(hold) or any(v not in views for v in hold):
+            ap.error(f"--field_holdout must name distinct views of --views {views}, got {hold}")
+        if len(set(views)) != len(views) or len(views) - len(hold) < 3:
+            ap.error(f"--field_holdout needs at least 3 distinct --views that are not held out, got {views} "
+                     f"without {hold}")
     return args
 
 
@@ -170,8 +192,8 @@ def run(args) -> dict:
                 save_png(grey[j], os.path.join(d, f"std_{wv:g}.png"))
 
     t1 = time.time()
-    rows, _, *rest = evaluate_objects(model, objects, args.input_view, views, w, args.timesteps, args.batch,
-                                      args.autoregressive, args.seed, dev,
+    rows, kept, *rest = evaluate_objects(model, objects, args.input_view, views, w, args.timesteps, args.batch,
+                                      args.autoregressive, args.seed, dev, keep_images=bool(args.field_holdout),
                                       on_view=write_pngs if args.save_png else None, solver=args.sampler,
                                       eta=args.eta, spacing=args.spacing, prediction=prediction,
                                       consistency=args.consistency, samples=C)
@@ -187,6 +209,15 @@ def run(args) -> dict:
     if C > 1:
         from distributed_3d_diffusion_pytorch_amd.engine import summarize_ensemble
         result["ensemble"] = {"per_w": summarize_ensemble(rest[-1]), "rows": rest[-1]}
+    if args.field_holdout:
+        from distributed_3d_diffusion_pytorch_amd.engine import field_rows, summarize_field
+        hold = [int(v) for v in args.field_holdout.split(",")]
+        fit = {"grid": args.field_grid, "seed": args.seed, **({"iters": args.field_iters} if args.field_iters else {})}
+        frows = field_rows(objects, kept, views, hold, w, dev, **fit)
+        result["field"] = {"per_w": summarize_field(frows), "rows": frows}
+        if args.procedural:
+            grows = field_rows(objects, None, views, hold, w, dev, **fit)
+            result["field"]["gt_field"] = {**summarize_field(grows)["gt"], "rows": grows}
     if args.val_batches > 0:
         result["val_loss"], bins = val_loss(model, cfg, args, dev, prediction)
         if bins is not None:
@@ -222,6 +253,14 @@ def run(args) -> dict:
                 print(f"[evaluate] w={k}: spread co-visible {num(d['covisible']['spread'], '.3e')}  disoccluded "
                       f"{num(d['disoccluded']['spread'], '.3e')}  background "
                       f"{num(d['background']['spread'], '.3e')}", flush=True)
+    if args.field_holdout:
+        for k, d in sorted(result["field"]["per_w"].items(), key=lambda kv: float(kv[0])):
+            print(f"[evaluate] w={k}: field PSNR {d['field_psnr']:.3f} dB  SSIM {d['field_ssim']:.4f} on the held-out "
+                  f"views {args.field_holdout}", flush=True)
+        if args.procedural:
+            d = result["field"]["gt_field"]
+            print(f"[evaluate] ground-truth ceiling: field PSNR {d['field_psnr']:.3f} dB  SSIM "
+                  f"{d['field_ssim']:.4f}", flush=True)
     print(f"[evaluate] {result['n_images']} images ({result['n_identical']} identical) in "
           f"{result['wall_seconds']:.2f}s -> {os.path.join(args.out, 'metrics.json')}", flush=True)
     return result

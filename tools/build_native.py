@@ -25,7 +25,8 @@ OBJ = os.path.join(ROOT, "build", "native")
 ARCH = os.environ.get("D3D_OFFLOAD_ARCH", "gfx950")
 # Flags of single translation units.  attention_hd.hip: scalar fp32 VALU only
 # (no packed fp32 add / mul / fma forms in the accumulator rescales).
-FILE_FLAGS = {"attention_hd.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]}
+_NO_PK_F32 = ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]
+FILE_FLAGS = {"attention_hd.hip": _NO_PK_F32, "field.hip": _NO_PK_F32}
 
 
 def hipcc() -> str:
