@@ -3,9 +3,9 @@ from .trainer import Trainer
 from .sampler import DiffusionSampler, RecordEntry, SolverState, shard_range
 from .evaluate import (EvalObject, evaluate_objects, gt_ceiling, heldout_loss, load_objects, summarize,
                        summarize_consistency, summarize_ensemble)
-from .field import field_consistency, field_rows, fit_field, summarize_field
+from .field import field_consistency, field_rows, fit_field, fit_fields, summarize_field
 
 __all__ = ["FusedAdam", "ema_decay_for", "warmup_lr", "Trainer", "DiffusionSampler", "RecordEntry", "SolverState",
            "shard_range", "EvalObject", "evaluate_objects", "heldout_loss", "load_objects", "summarize",
-           "summarize_consistency", "summarize_ensemble", "gt_ceiling", "fit_field", "field_consistency", "field_rows",
-           "summarize_field"]
+           "summarize_consistency", "summarize_ensemble", "gt_ceiling", "fit_field", "fit_fields", "field_consistency",
+           "field_rows", "summarize_field"]

@@ -68,23 +68,55 @@ def fit_field(images, R, t, K, *, grid: int = 48, samples: int = 64, bound: floa
     return g.detach(), history
 
 
-def field_consistency(images, R, t, K, train: Sequence[int], test: Sequence[int], **fit) -> dict:
-    """The score of one set of views: fit a field (:func:`fit_field`, ``fit``
-    its keywords) to ``images[train]``, render the poses of ``test`` and score
-    the renders against ``images[test]`` with ``ops.image_metrics`` (as 8-bit
-    PNGs).  Returns ``field_psnr`` / ``field_ssim`` (the means over the test
-    views; a view rendered exactly counts with 100 dB), ``field_psnr_views`` /
-    ``field_ssim_views``, ``fit_loss`` (the last iteration's mean loss) and
-    ``n_train`` / ``n_test``.  Fewer than 3 training views, or no test view,
-    is a ValueError."""
-    train, test = [int(v) for v in train], [int(v) for v in test]
-    if len(train) < 3:
-        raise ValueError(f"field_consistency needs at least 3 training views, got {len(train)}")
-    if not test:
-        raise ValueError("field_consistency needs at least one held-out view")
+def fit_fields(images, R, t, K, *, tv_rgb: float = 0.0, tv_sigma: float = 0.0, grid: int = 48, samples: int = 64,
+               bound: float = 1.0, iters: int = FIT_ITERS, rays_per_iter: int = FIT_RAYS, lr: float = FIT_LR,
+               seed: int = 0, rescale_from: int = 128):
+    """F independent field fits at once: ``images`` [F,V,3,H,W] in [-1, 1],
+    ``R`` [F,V,3,3], ``t`` [F,V,3] and one ``K`` [3,3] as :func:`fit_field`
+    takes them.  The rays of all fields are computed once; after that
+    iteration i is two ops for all fields together, with no host synchronise:
+    ``ops.field_batch_loss_grad`` draws ``rays_per_iter`` of the V H W rays by
+    the counter hash of ``(seed, i)`` (with replacement, unsorted -- unlike
+    :func:`fit_field`, which sorts its draw -- and the same for every field)
+    and ``ops.field_adam_tv`` takes the Adam step of rate ``lr`` on the mean
+    squared error plus the smoothness term ``tv_rgb`` / ``tv_sigma`` (the
+    weights of ``L_tv``, see the op) between two ping-ponged grids, from zero.
+    A batched fit equals the F single fits bit for bit on a given backend.
+    Returns ``(grids [F,grid,grid,grid,4], history fp64 [iters,F])``, the
+    per-iteration mean loss (over rays and channels) of every field."""
+    if images.dim() != 5 or images.shape[2] != 3:
+        raise ValueError(f"fit_fields: images must be [F,V,3,H,W], got {tuple(images.shape)}")
+    F, V, _, H, W = (int(s) for s in images.shape)
+    if tuple(R.shape) != (F, V, 3, 3) or tuple(t.shape) != (F, V, 3) or tuple(K.shape) != (3, 3):
+        raise ValueError(f"fit_fields: R, t, K must be [{F},{V},3,3], [{F},{V},3], [3,3], got {tuple(R.shape)}, "
+                         f"{tuple(t.shape)}, {tuple(K.shape)}")
+    if iters < 1 or rays_per_iter < 1:
+        raise ValueError(f"fit_fields: iters and rays_per_iter must be at least 1, got {iters} and {rays_per_iter}")
+    dev = images.device
+    n = int(rays_per_iter)
+    g = [torch.zeros(F, grid, grid, grid, 4, dtype=torch.float32, device=dev) for _ in range(2)]
+    if F == 0:
+        return g[0], torch.zeros(iters, 0, dtype=torch.float64, device=dev)
+    # per field, so that a field's rays do not depend on the batch it is fitted in
+    rays = [_rays(R[f].to(dev), t[f].to(dev), K.to(dev), H, W, rescale_from) for f in range(F)]
+    o = torch.stack([r[0] for r in rays]).contiguous()
+    d = torch.stack([r[1] for r in rays]).contiguous()
+    y = images.float().permute(0, 1, 3, 4, 2).reshape(F, -1, 3).contiguous()
+    m, v = torch.zeros_like(g[0]), torch.zeros_like(g[0])
+    losses = []
+    for it in range(iters):
+        cur, nxt = g[it & 1], g[1 - (it & 1)]
+        loss, grad = ops.field_batch_loss_grad(cur, o, d, y, n=n, it=it, seed=seed, samples=samples, bound=bound)
+        ops.field_adam_tv(cur, nxt, m, v, grad, step=it + 1, lr=lr, grad_scale=1.0 / (3.0 * n), tv_rgb=tv_rgb,
+                          tv_sigma=tv_sigma)
+        losses.append(loss)
+    return g[iters & 1], torch.stack(losses) / (3.0 * n)
+
+
+def _score(grid, fit_loss: float, images, R, t, K, train, test, fit) -> dict:
+    """The row of one fitted field: its renders of the poses of ``test`` against ``images[test]``."""
     H, W = (int(s) for s in images.shape[-2:])
     dev = images.device
-    grid, history = fit_field(images[train], R[train], t[train], K, **fit)
     o, d = _rays(R[test].to(dev), t[test].to(dev), K.to(dev), H, W, fit.get("rescale_from", 128))
     C = ops.field_render(grid, o, d, samples=fit.get("samples", 64), bound=fit.get("bound", 1.0), width=W)
     pred = (C.view(len(test), H, W, 3).permute(0, 3, 1, 2) * 2.0 - 1.0).contiguous()
@@ -92,17 +124,57 @@ def field_consistency(images, R, t, K, train: Sequence[int], test: Sequence[int]
     psnr = [10.0 * math.log10(1.0 / m) if m > 0 else 100.0 for m in mse.double().cpu().tolist()]
     ssim = ssim.double().cpu().tolist()
     return {"field_psnr": sum(psnr) / len(psnr), "field_ssim": sum(ssim) / len(ssim), "field_psnr_views": psnr,
-            "field_ssim_views": ssim, "fit_loss": float(history[-1]), "n_train": len(train), "n_test": len(test)}
+            "field_ssim_views": ssim, "fit_loss": fit_loss, "n_train": len(train), "n_test": len(test)}
+
+
+def _split(train, test):
+    train, test = [int(v) for v in train], [int(v) for v in test]
+    if len(train) < 3:
+        raise ValueError(f"field_consistency needs at least 3 training views, got {len(train)}")
+    if not test:
+        raise ValueError("field_consistency needs at least one held-out view")
+    return train, test
+
+
+def _batched(batch: int, tv_rgb: float, tv_sigma: float) -> bool:
+    if isinstance(batch, bool) or not isinstance(batch, int) or batch < 1:
+        raise ValueError(f"batch must be an integer >= 1, got {batch!r}")
+    return batch > 1 or tv_rgb != 0.0 or tv_sigma != 0.0
+
+
+def field_consistency(images, R, t, K, train: Sequence[int], test: Sequence[int], *, batch: int = 1,
+                      tv_rgb: float = 0.0, tv_sigma: float = 0.0, **fit) -> dict:
+    """The score of one set of views: fit a field (:func:`fit_field`, ``fit``
+    its keywords) to ``images[train]``, render the poses of ``test`` and score
+    the renders against ``images[test]`` with ``ops.image_metrics`` (as 8-bit
+    PNGs).  With ``batch > 1`` or a non-zero ``tv_rgb`` / ``tv_sigma`` the fit
+    is :func:`fit_fields` (here of one field) with that smoothness term.
+    Returns ``field_psnr`` / ``field_ssim`` (the means over the test
+    views; a view rendered exactly counts with 100 dB), ``field_psnr_views`` /
+    ``field_ssim_views``, ``fit_loss`` (the last iteration's mean loss) and
+    ``n_train`` / ``n_test``.  Fewer than 3 training views, or no test view,
+    is a ValueError."""
+    train, test = _split(train, test)
+    if _batched(batch, tv_rgb, tv_sigma):
+        grids, history = fit_fields(images[train][None], R[train][None], t[train][None], K, tv_rgb=tv_rgb,
+                                    tv_sigma=tv_sigma, **fit)
+        grid, history = grids[0], history[:, 0]
+    else:
+        grid, history = fit_field(images[train], R[train], t[train], K, **fit)
+    return _score(grid, float(history[-1]), images, R, t, K, train, test, fit)
 
 
 def field_rows(objects, images: Dict[tuple, torch.Tensor], views: Sequence[int], holdout: Sequence[int],
-               w: Sequence[float], device=None, **fit) -> List[dict]:
+               w: Sequence[float], device=None, *, batch: int = 1, tv_rgb: float = 0.0, tv_sigma: float = 0.0,
+               **fit) -> List[dict]:
     """One :func:`field_consistency` row per (object, guidance weight) of an
     ``evaluate_objects(..., keep_images=True)`` run: ``images[(instance, view)]``
     the generated ``[len(w),3,H,W]`` batch; the views in ``holdout`` are held
     out, the other generated views are the training set.  ``images`` None:
     the objects' own (ground-truth) images, one row per object with ``w``
-    None -- the ceiling of the score at this grid and view count."""
+    None -- the ceiling of the score at this grid and view count.  With
+    ``batch > 1`` or a non-zero ``tv_rgb`` / ``tv_sigma`` the fields are fitted
+    by :func:`fit_fields`, at most ``batch`` (object, weight) pairs per call."""
     views, holdout = [int(v) for v in views], [int(v) for v in holdout]
     bad = [v for v in holdout if v not in views]
     if bad or len(set(holdout)) != len(holdout):
@@ -110,14 +182,36 @@ def field_rows(objects, images: Dict[tuple, torch.Tensor], views: Sequence[int],
     train = [i for i, v in enumerate(views) if v not in holdout]
     test = [i for i, v in enumerate(views) if v in holdout]
     dev = torch.device(device) if device is not None else torch.device("cpu")
-    rows = []
+    batched = _batched(batch, tv_rgb, tv_sigma)
+    rows, todo = [], []
+
+    def flush():
+        """Fit and score the pending (object, weight) pairs in one fit_fields call."""
+        tr, te = _split(train, test)
+        grids, history = fit_fields(torch.stack([p[2][tr] for p in todo]), torch.stack([p[3][tr] for p in todo]),
+                                    torch.stack([p[4][tr] for p in todo]), todo[0][5], tv_rgb=tv_rgb,
+                                    tv_sigma=tv_sigma, **fit)
+        last = history[-1].cpu().tolist()
+        for f, (name, wv, img, R, t, K) in enumerate(todo):
+            rows.append({"instance": name, "w": wv, **_score(grids[f], last[f], img, R, t, K, tr, te, fit)})
+        todo.clear()
+
     for o in objects:
         R = torch.stack([o.R[v] for v in views]).to(dev)
         t = torch.stack([o.T[v] for v in views]).to(dev)
         for i, wv in enumerate(w if images is not None else (None,)):
             img = torch.stack([o.imgs[v] if images is None else images[(o.name, v)][i] for v in views]).to(dev)
-            rows.append({"instance": o.name, "w": None if wv is None else float(wv),
-                         **field_consistency(img.float(), R, t, o.K.to(dev), train, test, **fit)})
+            wv = None if wv is None else float(wv)
+            if not batched:
+                rows.append({"instance": o.name, "w": wv,
+                             **field_consistency(img.float(), R, t, o.K.to(dev), train, test, **fit)})
+                continue
+            K = o.K.to(dev)
+            if todo and (len(todo) == batch or not torch.equal(K, todo[0][5])):     # one K per fit_fields call
+                flush()
+            todo.append((o.name, wv, img.float(), R, t, K))
+    if todo:
+        flush()
     return rows
 
 

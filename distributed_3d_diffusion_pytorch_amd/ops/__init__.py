@@ -340,6 +340,50 @@ def field_loss_grad(grid, rays_o, rays_d, target, *, samples: int, bound: float 
     return impl.field_loss_grad(grid, rays_o, rays_d, target, samples=samples, bound=bound, width=width)
 
 
+def field_batch_loss_grad(grid, rays_o, rays_d, target, *, n: int, it: int, seed: int, samples: int,
+                          bound: float = 1.0):
+    """``(loss, grad)`` of iteration ``it`` of F independent field fits:
+    ``grid`` fp32 ``[F,G,G,G,4]``; ``rays_o``, ``rays_d`` and ``target`` fp32
+    ``[F,N,3]``, the N stored rays of every field.  The op draws the ``n`` rays
+    of the iteration itself -- slot s < n takes ray
+    ``hash_u32(seed, s + it * n) % N``, with replacement, unsorted, the same
+    for every field -- and returns per field what :func:`field_loss_grad`
+    returns on those rows: ``loss`` fp64 ``[F]`` (a sum) and ``grad`` fp32
+    ``[F,G,G,G,4]``, bitwise reproducible; field f reads row f of every input
+    only.  ``n * samples`` beyond the fixed-point range is a ValueError, as
+    there.  HIP (``csrc/field_fit.hip``, which states the rule) on the GPU
+    without a host synchronise, the float64 torch form on the CPU."""
+    F, G, _ = _t.field_batch_check("field_batch_loss_grad", grid, rays_o, rays_d, target, n=n, it=it, seed=seed,
+                                   samples=samples, bound=bound)
+    if F == 0:
+        return (torch.zeros(0, dtype=torch.float64, device=grid.device),
+                torch.zeros(0, G, G, G, 4, dtype=torch.float32, device=grid.device))
+    impl = _h() if grid.is_cuda and use_hip(grid, any_dtype=True) else _t
+    return impl.field_batch_loss_grad(grid, rays_o, rays_d, target, n=n, it=it, seed=seed, samples=samples,
+                                      bound=bound)
+
+
+def field_adam_tv(grid, grid_out, exp_avg, exp_avg_sq, grad, *, step: int, lr: float, betas=(0.9, 0.999),
+                  eps: float = 1e-8, grad_scale: float = 1.0, tv_rgb: float = 0.0, tv_sigma: float = 0.0):
+    """One Adam step with a smoothness term on F voxel fields, all tensors
+    fp32 ``[F,G,G,G,4]`` and contiguous: on ``g = grad_scale * grad +
+    grad L_tv(grid)`` with ``L_tv = (1 / G^3) sum_c lambda_c sum_edges
+    (v_a,c - v_b,c)^2`` over the axis-aligned neighbour pairs inside the grid
+    (``lambda_c`` is ``tv_rgb`` for the colour channels, ``tv_sigma`` for the
+    density), Adam in ``torch.optim.Adam``'s arithmetic with the 1-based
+    ``step``.  Writes the new grid to ``grid_out`` and updates ``exp_avg`` and
+    ``exp_avg_sq`` in place; ``grid`` is left as it is -- the caller
+    ping-pongs two grids, and tensors that share memory are a ValueError.
+    Returns nothing.  HIP (``csrc/field_fit.hip``) on the GPU, the float64
+    torch form on the CPU."""
+    kw = dict(step=step, lr=lr, betas=betas, eps=eps, grad_scale=grad_scale, tv_rgb=tv_rgb, tv_sigma=tv_sigma)
+    F, _ = _t.field_adam_check("field_adam_tv", grid, grid_out, exp_avg, exp_avg_sq, grad, **kw)
+    if F == 0:
+        return
+    impl = _h() if grid.is_cuda and use_hip(grid, any_dtype=True) else _t
+    impl.field_adam_tv(grid, grid_out, exp_avg, exp_avg_sq, grad, **kw)
+
+
 def psnr(mse):
     """``10 log10(1 / mse)`` on the [0, 1] scale; ``+inf`` where ``mse == 0``."""
     return -10.0 * torch.log10(torch.as_tensor(mse, dtype=torch.float32))
@@ -351,7 +395,7 @@ posenc_nerf = _t.posenc_nerf
 
 __all__ = ["diffusion_inputs", "diff_loss_nhwc", "diff_loss_rows", "loss_bins_add", "group_norm", "gn_film", "conv3x3", "linear", "film_batch", "cat_gn_silu_dense", "cond_conv", "ray_posenc_dir",
            "ray_origin_pe", "ray_conditioning", "attention", "avgpool2", "upsample2",
-           "silu", "logsnr_mlp", "ray_posenc", "image_metrics", "scene_render", "view_consistency", "ensemble_stats", "field_render", "field_loss_grad", "psnr", "posenc_ddpm", "camera_rays", "posenc_nerf", "set_backend",
+           "silu", "logsnr_mlp", "ray_posenc", "image_metrics", "scene_render", "view_consistency", "ensemble_stats", "field_render", "field_loss_grad", "field_batch_loss_grad", "field_adam_tv", "psnr", "posenc_ddpm", "camera_rays", "posenc_nerf", "set_backend",
            "use_hip", "load_library", "library_error", "lib_path"]
 
 

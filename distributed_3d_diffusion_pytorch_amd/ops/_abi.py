@@ -137,6 +137,11 @@ SIGNATURES = {
     "d3d_field_blocks": [I, I],
     "d3d_field_render": [P, P, P, P, I, I, I, C.c_double, I, P],
     "d3d_field_loss_grad": [P, P, P, P, P, P, P, P, I, I, I, C.c_double, I, P],
+    # field_fit.hip
+    "d3d_field_fit_blocks": [I],
+    "d3d_field_fit_loss_grad": [P, P, P, P, P, P, P, P, I, L, I, L, U64, I, I, C.c_double, P],
+    "d3d_field_adam_tv": [P, P, P, P, P, I, I, I, C.c_double, C.c_double, C.c_double, C.c_double, C.c_double,
+                          C.c_double, C.c_double, P],
 }
 
 

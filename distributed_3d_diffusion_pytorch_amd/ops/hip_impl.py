@@ -3024,3 +3024,43 @@ def field_loss_grad(grid, rays_o, rays_d, target, *, samples, bound=1.0, width=0
                                   G, float(bound), int(width), _st()), "field_loss_grad")
     _FIELD_ACC[key] = acc                          # (a failed launch drops it: its contents are unknown)
     return loss, grad
+
+
+# ------------------------------------------------------ batched field fits ---
+def field_batch_loss_grad(grid, rays_o, rays_d, target, *, n, it, seed, samples, bound=1.0):
+    """(loss fp64 [F], grad fp32 [F,G,G,G,4]) of iteration ``it`` of F field
+    fits (csrc/field_fit.hip: launch grid (ceil(n / 256), F), every thread
+    draws its ray and runs field.hip's two walks into field f's slice of the
+    fixed-point accumulator; bitwise reproducible, no host synchronise)."""
+    F, G, N = _t.field_batch_check("field_batch_loss_grad", grid, rays_o, rays_d, target, n=n, it=it, seed=seed,
+                                   samples=samples, bound=bound)
+    dev = grid.device
+    loss = torch.empty(F, dtype=torch.float64, device=dev)
+    grad = torch.empty(F, G, G, G, 4, dtype=F32, device=dev)
+    if F == 0:
+        return loss, grad
+    key = (dev, F, G)
+    acc = _FIELD_ACC.pop(key, None)
+    if acc is None:
+        acc = torch.zeros(F * G * G * G * 4, dtype=torch.int64, device=dev)
+    part = torch.empty(F * _lib.d3d_field_fit_blocks(int(n)), dtype=torch.float64, device=dev)
+    _chk(_lib.d3d_field_fit_loss_grad(grid.data_ptr(), rays_o.data_ptr(), rays_d.data_ptr(), target.data_ptr(),
+                                      acc.data_ptr(), part.data_ptr(), loss.data_ptr(), grad.data_ptr(), F, N, int(n),
+                                      int(it), int(seed) & _t._M64, int(samples), G, float(bound), _st()),
+         "field_batch_loss_grad")
+    _FIELD_ACC[key] = acc                          # (a failed launch drops it: its contents are unknown)
+    return loss, grad
+
+
+def field_adam_tv(grid, grid_out, exp_avg, exp_avg_sq, grad, *, step, lr, betas=(0.9, 0.999), eps=1e-8,
+                  grad_scale=1.0, tv_rgb=0.0, tv_sigma=0.0):
+    """Adam with the smoothness term on F grids (csrc/field_fit.hip: one
+    workgroup per 8 x 8 x 8 tile, the tile and its halo staged in LDS; the new
+    grid goes to ``grid_out``, the moments are updated in place)."""
+    F, G = _t.field_adam_check("field_adam_tv", grid, grid_out, exp_avg, exp_avg_sq, grad, step=step, lr=lr,
+                               betas=betas, eps=eps, grad_scale=grad_scale, tv_rgb=tv_rgb, tv_sigma=tv_sigma)
+    if F == 0:
+        return
+    _chk(_lib.d3d_field_adam_tv(grid.data_ptr(), grid_out.data_ptr(), exp_avg.data_ptr(), exp_avg_sq.data_ptr(),
+                                grad.data_ptr(), F, G, int(step), float(lr), float(betas[0]), float(betas[1]),
+                                float(eps), float(grad_scale), float(tv_rgb), float(tv_sigma), _st()), "field_adam_tv")

@@ -925,3 +925,164 @@ def field_loss_grad(grid, rays_o, rays_d, target, *, samples, bound=1.0, width=0
         L = (C - (target.to(dtype) + 1) * 0.5).square().sum()
         grad, = torch.autograd.grad(L, g)
     return L.detach().double(), grad.float()
+
+
+# ------------------------------------------------------ batched field fits ---
+# One iteration of F independent field fits as two ops: the data term over
+# rays drawn by the counter hash, and Adam with a smoothness term on the grid
+# (csrc/field_fit.hip holds the rule in full).
+FIELD_MAX_BATCH = 65535              # the launch grid's second dimension
+
+
+def field_draw(seed: int, it: int, n: int, N: int, device=None) -> torch.Tensor:
+    """The rays of iteration ``it``: slot s < n takes ``hash_u32(seed, s + it n) % N``
+    (with replacement, unsorted, the same for every field)."""
+    return hash_u32(seed, torch.arange(n, dtype=torch.int64, device=device) + it * n) % N
+
+
+def _field_tensors(name, named, dev):
+    for nm, x in named:
+        if not isinstance(x, torch.Tensor):
+            raise ValueError(f"{name}: {nm} must be a tensor, got {type(x).__name__}")
+        if x.device != dev:
+            raise ValueError(f"{name}: {nm} is on {x.device}, the grid on {dev}")
+        if x.dtype != torch.float32:
+            raise ValueError(f"{name}: {nm} must be float32, got {x.dtype}")
+        if not x.is_contiguous():
+            raise ValueError(f"{name}: {nm} must be contiguous")
+
+
+def _field_batch_grid(name, grid):
+    if grid.dim() != 5 or grid.shape[4] != 4 or not grid.shape[1] == grid.shape[2] == grid.shape[3]:
+        raise ValueError(f"{name}: grid must be [F,G,G,G,4], got {tuple(grid.shape)}")
+    F, G = int(grid.shape[0]), int(grid.shape[1])
+    if G < 2:
+        raise ValueError(f"{name}: the grid needs at least 2 nodes per axis, got G = {G}")
+    if F > FIELD_MAX_BATCH:
+        raise ValueError(f"{name}: at most {FIELD_MAX_BATCH} fields per call, got {F}")
+    return F, G
+
+
+def _is_int(x) -> bool:
+    return isinstance(x, int) and not isinstance(x, bool)
+
+
+def field_batch_check(name, grid, rays_o, rays_d, target, *, n, it, seed, samples, bound):
+    """Argument check shared by both backends (ValueError); returns (F, G, N)."""
+    if not isinstance(grid, torch.Tensor):
+        raise ValueError(f"{name}: grid must be a tensor, got {type(grid).__name__}")
+    _field_tensors(name, (("grid", grid), ("rays_o", rays_o), ("rays_d", rays_d), ("target", target)), grid.device)
+    F, G = _field_batch_grid(name, grid)
+    if rays_o.dim() != 3 or rays_o.shape[0] != F or rays_o.shape[2] != 3:
+        raise ValueError(f"{name}: rays_o must be [{F},N,3], got {tuple(rays_o.shape)}")
+    N = int(rays_o.shape[1])
+    for nm, x in (("rays_d", rays_d), ("target", target)):
+        if tuple(x.shape) != (F, N, 3):
+            raise ValueError(f"{name}: {nm} must be [{F}, {N}, 3] as rays_o, got {tuple(x.shape)}")
+    if N < 1 or N >= 1 << 31:
+        raise ValueError(f"{name}: every field needs between 1 and 2^31 - 1 stored rays, got N = {N}")
+    if not _is_int(n) or n < 1 or n >= 1 << 31:
+        raise ValueError(f"{name}: n must be an integer >= 1, got {n!r}")
+    if not _is_int(it) or it < 0 or it >= 1 << 31:
+        raise ValueError(f"{name}: it must be an integer >= 0, got {it!r}")
+    if not _is_int(seed):
+        raise ValueError(f"{name}: seed must be an integer, got {seed!r}")
+    if not _is_int(samples) or samples < 1:
+        raise ValueError(f"{name}: samples must be an integer >= 1, got {samples!r}")
+    if not (isinstance(bound, (int, float)) and 0.0 < float(bound) < float("inf")):
+        raise ValueError(f"{name}: bound must be a positive finite number, got {bound!r}")
+    if field_fix_load(n, samples, float(bound)) > FIELD_FIX_BUDGET:
+        raise ValueError(f"{name}: n * samples = {n * samples} is beyond the gradient's fixed-point range "
+                         f"(n S 6 max(1, 2 sqrt(3) bound / S) <= 2^23 per field); draw fewer rays per iteration")
+    return F, G, N
+
+
+def field_batch_loss_grad(grid, rays_o, rays_d, target, *, n, it, seed, samples, bound=1.0, dtype=torch.float64):
+    """(loss fp64 [F], grad fp32 [F,G,G,G,4]): the float64 torch form of
+    csrc/field_fit.hip's data term -- per field, :func:`field_loss_grad` on the
+    rows :func:`field_draw` names (``dtype``: the precision it is evaluated in)."""
+    F, G, N = field_batch_check("field_batch_loss_grad", grid, rays_o, rays_d, target, n=n, it=it, seed=seed,
+                                samples=samples, bound=bound)
+    idx = field_draw(seed, it, n, N, grid.device)
+    loss = torch.zeros(F, dtype=torch.float64, device=grid.device)
+    grad = torch.zeros_like(grid)
+    for f in range(F):
+        loss[f], grad[f] = field_loss_grad(grid[f], rays_o[f][idx], rays_d[f][idx], target[f][idx], samples=samples,
+                                           bound=bound, dtype=dtype)
+    return loss, grad
+
+
+def field_tv_grad(grid, tv_rgb: float, tv_sigma: float, dtype=torch.float64):
+    """The gradient of ``L_tv = (1 / G^3) sum_c lambda_c sum_edges (v_a - v_b)^2``
+    on ``grid`` [...,G,G,G,4] in ``dtype``: ``(2 lambda_c / G^3) sum_neighbours
+    (v - v_n)`` over the neighbours inside the grid, in the kernel's order
+    x-1, x+1, y-1, y+1, z-1, z+1."""
+    v = grid.to(dtype)
+    G = v.shape[-2]
+    tv = torch.zeros_like(v)
+    for dim in (-2, -3, -4):
+        lo, hi = v.narrow(dim, 0, G - 1), v.narrow(dim, 1, G - 1)
+        tv.narrow(dim, 1, G - 1).add_(hi - lo)
+        tv.narrow(dim, 0, G - 1).add_(lo - hi)
+    g3 = float(G) ** 3
+    coef = torch.tensor([2.0 * tv_rgb / g3] * 3 + [2.0 * tv_sigma / g3], dtype=dtype, device=v.device)
+    return coef * tv
+
+
+def field_adam_tv_math(p, m, v, grad, *, step, lr, betas=(0.9, 0.999), eps=1e-8, grad_scale=1.0, tv_rgb=0.0,
+                       tv_sigma=0.0, dtype=torch.float64):
+    """(p', m', v') in ``dtype``: one Adam step in torch's arithmetic order on
+    ``grad_scale grad + grad L_tv(p)`` (csrc/field_fit.hip states it)."""
+    b1, b2 = float(betas[0]), float(betas[1])
+    p, m, v = p.to(dtype), m.to(dtype), v.to(dtype)
+    g = grad.to(dtype) * grad_scale + field_tv_grad(p, tv_rgb, tv_sigma, dtype)
+    m = m + (1.0 - b1) * (g - m)
+    v = v * b2 + (1.0 - b2) * g * g
+    denom = v.sqrt() / math.sqrt(1.0 - b2 ** step) + eps
+    return p - (lr / (1.0 - b1 ** step)) * (m / denom), m, v
+
+
+def field_adam_check(name, grid, grid_out, exp_avg, exp_avg_sq, grad, *, step, lr, betas, eps, grad_scale, tv_rgb,
+                     tv_sigma):
+    """Argument check shared by both backends (ValueError); returns (F, G)."""
+    if not isinstance(grid, torch.Tensor):
+        raise ValueError(f"{name}: grid must be a tensor, got {type(grid).__name__}")
+    named = (("grid", grid), ("grid_out", grid_out), ("exp_avg", exp_avg), ("exp_avg_sq", exp_avg_sq), ("grad", grad))
+    _field_tensors(name, named, grid.device)
+    F, G = _field_batch_grid(name, grid)
+    for nm, x in named[1:]:
+        if x.shape != grid.shape:
+            raise ValueError(f"{name}: {nm} must be {tuple(grid.shape)} as grid, got {tuple(x.shape)}")
+    span = [(nm, x.data_ptr(), x.data_ptr() + x.numel() * 4) for nm, x in named if x.numel()]
+    for i, (na, a0, a1) in enumerate(span):
+        for nb, b0, b1 in span[i + 1:]:
+            if a0 < b1 and b0 < a1:
+                raise ValueError(f"{name}: {na} and {nb} share memory; the new grid goes to a second buffer "
+                                 f"(ping-pong two grids) and every state tensor is its own")
+    if not _is_int(step) or step < 1:
+        raise ValueError(f"{name}: step counts from 1, got {step!r}")
+    try:
+        b1, b2 = (float(b) for b in betas)
+        scal = {"lr": float(lr), "eps": float(eps), "grad_scale": float(grad_scale), "tv_rgb": float(tv_rgb),
+                "tv_sigma": float(tv_sigma)}
+    except (TypeError, ValueError):
+        raise ValueError(f"{name}: lr, betas, eps, grad_scale, tv_rgb and tv_sigma must be numbers") from None
+    if not (0.0 <= b1 < 1.0 and 0.0 <= b2 < 1.0):
+        raise ValueError(f"{name}: betas must lie in [0, 1), got {betas!r}")
+    for nm, x in scal.items():
+        if not math.isfinite(x) or (nm != "grad_scale" and x < 0.0):
+            raise ValueError(f"{name}: {nm} must be finite{'' if nm == 'grad_scale' else ' and not negative'}, got {x!r}")
+    return F, G
+
+
+def field_adam_tv(grid, grid_out, exp_avg, exp_avg_sq, grad, *, step, lr, betas=(0.9, 0.999), eps=1e-8,
+                  grad_scale=1.0, tv_rgb=0.0, tv_sigma=0.0, dtype=torch.float64):
+    """The float64 torch form of csrc/field_fit.hip's update: writes the new
+    grid to ``grid_out`` and the moments in place, rounded to fp32 at the end."""
+    kw = dict(step=step, lr=lr, betas=betas, eps=eps, grad_scale=grad_scale, tv_rgb=tv_rgb, tv_sigma=tv_sigma)
+    field_adam_check("field_adam_tv", grid, grid_out, exp_avg, exp_avg_sq, grad, **kw)
+    with torch.no_grad():
+        p, m, v = field_adam_tv_math(grid, exp_avg, exp_avg_sq, grad, dtype=dtype, **kw)
+        grid_out.copy_(p)
+        exp_avg.copy_(m)
+        exp_avg_sq.copy_(v)

@@ -74,6 +74,12 @@ def parse(argv=None):
                          "against the held-out generated views; metrics.json gets a field block")
     ap.add_argument("--field_grid", type=int, default=48, help="--field_holdout: nodes per axis of the field")
     ap.add_argument("--field_iters", type=int, default=0, help="--field_holdout: fit iterations (0 = the default)")
+    ap.add_argument("--field_batch", type=int, default=1,
+                    help="--field_holdout: fit this many (object, w) fields per call (engine.fit_fields); 1 with "
+                         "--field_tv 0 is the one-by-one fit of engine.fit_field")
+    ap.add_argument("--field_tv", type=float, default=0.0,
+                    help="--field_holdout: weight of the smoothness term on the grid (colour and density alike); "
+                         "not 0 fits through engine.fit_fields (profiles/field/README.md recommends a value)")
     ap.add_argument("--timesteps", type=int, default=256)
     ap.add_argument("--sampler", default="ancestral", choices=["ancestral", "ddim", "dpmpp2m"],
                     help="update rule: the 256-step ancestral chain, DDIM or DPM-Solver++(2M) for few steps")
@@ -96,6 +102,9 @@ def parse(argv=None):
     args = ap.parse_args(argv)
     if args.samples < 1:
         ap.error(f"--samples must be at least 1, got {args.samples}")
+    if args.field_batch < 1 or not 0.0 <= args.field_tv < float("inf"):
+        ap.error(f"--field_batch must be at least 1 and --field_tv at least 0, got {args.field_batch} and "
+                 f"{args.field_tv}")
     if args.field_holdout:
         views = [int(v) for v in args.views.split(",")]
         hold = [int(v) for v in args.field_holdout.split(",")]
@@ -212,7 +221,8 @@ def run(args) -> dict:
     if args.field_holdout:
         from distributed_3d_diffusion_pytorch_amd.engine import field_rows, summarize_field
         hold = [int(v) for v in args.field_holdout.split(",")]
-        fit = {"grid": args.field_grid, "seed": args.seed, **({"iters": args.field_iters} if args.field_iters else {})}
+        fit = {"grid": args.field_grid, "seed": args.seed, **({"iters": args.field_iters} if args.field_iters else {}),
+               "batch": args.field_batch, "tv_rgb": args.field_tv, "tv_sigma": args.field_tv}
         frows = field_rows(objects, kept, views, hold, w, dev, **fit)
         result["field"] = {"per_w": summarize_field(frows), "rows": frows}
         if args.procedural:
