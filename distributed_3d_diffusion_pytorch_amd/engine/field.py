@@ -127,6 +127,44 @@ def _score(grid, fit_loss: float, images, R, t, K, train, test, fit) -> dict:
             "field_ssim_views": ssim, "fit_loss": fit_loss, "n_train": len(train), "n_test": len(test)}
 
 
+GEOM_KEYS = ("geom_n_truth", "geom_n_field", "geom_n_both", "geom_iou", "geom_depth_mae", "geom_depth_rmse",
+             "geom_normal_cos", "geom_sil_mse")
+
+
+def _geom_fields(sums: Sequence[float], pixels: int) -> dict:
+    """The ``geom_*`` fields of pooled ``ops.field_geometry`` rows: ``sums`` the
+    7 sums over all their views, ``pixels`` the pixels of those views.  Every
+    value is sum / count, None where its count is 0."""
+    nt, nf, nb = (int(round(x)) for x in sums[:3])
+    per = lambda x: x / nb if nb else None  # noqa: E731
+    mse = per(sums[4])
+    return {"geom_n_truth": nt, "geom_n_field": nf, "geom_n_both": nb,
+            "geom_iou": nb / (nt + nf - nb) if nt + nf - nb else None,
+            "geom_depth_mae": per(sums[3]), "geom_depth_rmse": None if mse is None else math.sqrt(mse),
+            "geom_normal_cos": None if nb == 0 else 1.0 - sums[5] / nb,
+            "geom_sil_mse": sums[6] / pixels if pixels else None,
+            "geom_sums": [float(x) for x in sums], "geom_pixels": int(pixels)}
+
+
+def _geometry(grids, scenes, R, t, K, H: int, W: int, fit) -> List[dict]:
+    """The ``geom_*`` fields of F fitted ``grids`` [F,G,G,G,4] seen from their
+    held-out cameras ``R`` [F,V,3,3], ``t`` [F,V,3] against the scene tables
+    ``scenes`` [F,6,16]: one ``ops.field_geometry`` call."""
+    F, V = int(R.shape[0]), int(R.shape[1])
+    dev = grids.device
+    scores = ops.field_geometry(grids.contiguous(), K.to(dev).double()[None].expand(F, 3, 3).contiguous(),
+                                R.to(dev).double(), t.to(dev).double(), H, W, samples=fit.get("samples", 64),
+                                bound=fit.get("bound", 1.0), rescale_from=fit.get("rescale_from", 128),
+                                table=scenes.to(dev).double().contiguous())
+    return [_geom_fields(row, V * H * W) for row in scores.sum(1).cpu().tolist()]
+
+
+def _need_scene(scene, name: str):
+    if scene is None:
+        raise ValueError(f"geometry needs the object's scene table (procedural objects carry one); {name} has none")
+    return scene
+
+
 def _split(train, test):
     train, test = [int(v) for v in train], [int(v) for v in test]
     if len(train) < 3:
@@ -143,7 +181,8 @@ def _batched(batch: int, tv_rgb: float, tv_sigma: float) -> bool:
 
 
 def field_consistency(images, R, t, K, train: Sequence[int], test: Sequence[int], *, batch: int = 1,
-                      tv_rgb: float = 0.0, tv_sigma: float = 0.0, **fit) -> dict:
+                      tv_rgb: float = 0.0, tv_sigma: float = 0.0, geometry: bool = False, scene=None,
+                      **fit) -> dict:
     """The score of one set of views: fit a field (:func:`fit_field`, ``fit``
     its keywords) to ``images[train]``, render the poses of ``test`` and score
     the renders against ``images[test]`` with ``ops.image_metrics`` (as 8-bit
@@ -152,21 +191,35 @@ def field_consistency(images, R, t, K, train: Sequence[int], test: Sequence[int]
     Returns ``field_psnr`` / ``field_ssim`` (the means over the test
     views; a view rendered exactly counts with 100 dB), ``field_psnr_views`` /
     ``field_ssim_views``, ``fit_loss`` (the last iteration's mean loss) and
-    ``n_train`` / ``n_test``.  Fewer than 3 training views, or no test view,
-    is a ValueError."""
+    ``n_train`` / ``n_test``.  ``geometry``: the fitted grid is also read out
+    with ``ops.field_geometry`` at the held-out poses against ``scene`` (the
+    object's fp64 [6,16] table; ValueError without one) and the row gains
+    ``geom_n_truth`` / ``geom_n_field`` / ``geom_n_both`` (pixels the scene,
+    the field, both hit), ``geom_iou``, ``geom_depth_mae`` /
+    ``geom_depth_rmse`` and ``geom_normal_cos`` over the pixels both hit and
+    ``geom_sil_mse``, each pooled over the held-out views as sum / count (None
+    where the count is 0; ``geom_sums`` / ``geom_pixels`` keep the sums for
+    further pooling).  Fewer than 3 training views, or no test view, is a
+    ValueError."""
     train, test = _split(train, test)
+    if geometry:
+        _need_scene(scene, "the object")
     if _batched(batch, tv_rgb, tv_sigma):
         grids, history = fit_fields(images[train][None], R[train][None], t[train][None], K, tv_rgb=tv_rgb,
                                     tv_sigma=tv_sigma, **fit)
         grid, history = grids[0], history[:, 0]
     else:
         grid, history = fit_field(images[train], R[train], t[train], K, **fit)
-    return _score(grid, float(history[-1]), images, R, t, K, train, test, fit)
+    row = _score(grid, float(history[-1]), images, R, t, K, train, test, fit)
+    if geometry:
+        H, W = (int(s) for s in images.shape[-2:])
+        row.update(_geometry(grid[None], scene[None], R[test][None], t[test][None], K, H, W, fit)[0])
+    return row
 
 
 def field_rows(objects, images: Dict[tuple, torch.Tensor], views: Sequence[int], holdout: Sequence[int],
                w: Sequence[float], device=None, *, batch: int = 1, tv_rgb: float = 0.0, tv_sigma: float = 0.0,
-               **fit) -> List[dict]:
+               geometry: bool = False, **fit) -> List[dict]:
     """One :func:`field_consistency` row per (object, guidance weight) of an
     ``evaluate_objects(..., keep_images=True)`` run: ``images[(instance, view)]``
     the generated ``[len(w),3,H,W]`` batch; the views in ``holdout`` are held
@@ -174,7 +227,11 @@ def field_rows(objects, images: Dict[tuple, torch.Tensor], views: Sequence[int],
     the objects' own (ground-truth) images, one row per object with ``w``
     None -- the ceiling of the score at this grid and view count.  With
     ``batch > 1`` or a non-zero ``tv_rgb`` / ``tv_sigma`` the fields are fitted
-    by :func:`fit_fields`, at most ``batch`` (object, weight) pairs per call."""
+    by :func:`fit_fields`, at most ``batch`` (object, weight) pairs per call.
+    ``geometry``: every row also gets the ``geom_*`` fields of
+    :func:`field_consistency` against the object's ``scene`` (ValueError for
+    an object without one); the batched path reads all grids of a
+    ``fit_fields`` call out in one ``ops.field_geometry`` call."""
     views, holdout = [int(v) for v in views], [int(v) for v in holdout]
     bad = [v for v in holdout if v not in views]
     if bad or len(set(holdout)) != len(holdout):
@@ -192,11 +249,17 @@ def field_rows(objects, images: Dict[tuple, torch.Tensor], views: Sequence[int],
                                     torch.stack([p[4][tr] for p in todo]), todo[0][5], tv_rgb=tv_rgb,
                                     tv_sigma=tv_sigma, **fit)
         last = history[-1].cpu().tolist()
-        for f, (name, wv, img, R, t, K) in enumerate(todo):
-            rows.append({"instance": name, "w": wv, **_score(grids[f], last[f], img, R, t, K, tr, te, fit)})
+        geom = [{}] * len(todo)
+        if geometry:
+            H, W = (int(s) for s in todo[0][2].shape[-2:])
+            geom = _geometry(grids, torch.stack([p[6] for p in todo]), torch.stack([p[3][te] for p in todo]),
+                             torch.stack([p[4][te] for p in todo]), todo[0][5], H, W, fit)
+        for f, (name, wv, img, R, t, K, _) in enumerate(todo):
+            rows.append({"instance": name, "w": wv, **_score(grids[f], last[f], img, R, t, K, tr, te, fit), **geom[f]})
         todo.clear()
 
     for o in objects:
+        scene = _need_scene(getattr(o, "scene", None), o.name) if geometry else None
         R = torch.stack([o.R[v] for v in views]).to(dev)
         t = torch.stack([o.T[v] for v in views]).to(dev)
         for i, wv in enumerate(w if images is not None else (None,)):
@@ -204,12 +267,13 @@ def field_rows(objects, images: Dict[tuple, torch.Tensor], views: Sequence[int],
             wv = None if wv is None else float(wv)
             if not batched:
                 rows.append({"instance": o.name, "w": wv,
-                             **field_consistency(img.float(), R, t, o.K.to(dev), train, test, **fit)})
+                             **field_consistency(img.float(), R, t, o.K.to(dev), train, test, geometry=geometry,
+                                                 scene=scene, **fit)})
                 continue
             K = o.K.to(dev)
             if todo and (len(todo) == batch or not torch.equal(K, todo[0][5])):     # one K per fit_fields call
                 flush()
-            todo.append((o.name, wv, img.float(), R, t, K))
+            todo.append((o.name, wv, img.float(), R, t, K, scene))
     if todo:
         flush()
     return rows
@@ -217,10 +281,15 @@ def field_rows(objects, images: Dict[tuple, torch.Tensor], views: Sequence[int],
 
 def summarize_field(rows: Sequence[dict]) -> dict:
     """Per guidance weight (``"gt"`` for the ground-truth rows) the means of
-    ``field_psnr``, ``field_ssim`` and ``fit_loss`` over the objects."""
+    ``field_psnr``, ``field_ssim`` and ``fit_loss`` over the objects; for rows
+    with ``geom_*`` fields also those, pooled over the objects as sum / count."""
     out = {}
     for wv in sorted({r["w"] for r in rows}, key=lambda x: -math.inf if x is None else x):
         sel = [r for r in rows if r["w"] == wv]
-        out["gt" if wv is None else f"{wv:g}"] = {"n": len(sel), **{k: sum(r[k] for r in sel) / len(sel)
-                                                                  for k in ("field_psnr", "field_ssim", "fit_loss")}}
+        d = {"n": len(sel), **{k: sum(r[k] for r in sel) / len(sel) for k in ("field_psnr", "field_ssim", "fit_loss")}}
+        if sel and all("geom_sums" in r for r in sel):
+            pooled = _geom_fields([sum(r["geom_sums"][k] for r in sel) for k in range(7)],
+                                  sum(r["geom_pixels"] for r in sel))
+            d.update({k: pooled[k] for k in GEOM_KEYS})
+        out["gt" if wv is None else f"{wv:g}"] = d
     return out

@@ -384,6 +384,34 @@ def field_adam_tv(grid, grid_out, exp_avg, exp_avg_sq, grad, *, step: int, lr: f
     impl.field_adam_tv(grid, grid_out, exp_avg, exp_avg_sq, grad, **kw)
 
 
+def field_geometry(grid, K, R, t, H: int, W: int, *, samples: int, bound: float = 1.0, rescale_from: int = 128,
+                   table=None, return_maps: bool = False):
+    """The surface F voxel fields imply, seen by V cameras each, and its score
+    against procedural truth: ``grid`` fp32 ``[F,G,G,G,4]`` (the layout of
+    ``engine.fit_fields``), ``K`` fp64 ``[F,3,3]`` (the intrinsics of the
+    ``rescale_from``-pixel image; 0: of this size), ``R`` fp64 ``[F,V,3,3]``
+    cam-to-world, ``t`` fp64 ``[F,V,3]``.  Every pixel-centre ray is walked as
+    :func:`field_render` walks it (``samples`` steps through
+    ``[-bound, bound]^3``): opacity ``A = sum w_i``; the field hits where ``A >
+    0.5``; there depth ``D = sum w_i t_i / A`` (``+inf`` elsewhere) and normal
+    ``n = -g / |g|``, ``g = sum w_i grad raw_sigma`` (zero elsewhere).  With
+    ``table`` fp64 ``[F,6,16]`` (``data.procedural_scene``) returns ``scores``
+    fp64 ``[F,V,7]``, sums over a view's pixels with ``M`` the true hit mask,
+    ``P`` the field's, ``t*`` / ``n*`` the true distance and normal: ``[sum M,
+    sum P, sum M&P, sum_{M&P} |D - t*|, sum_{M&P} (D - t*)^2, sum_{M&P} (1 - n
+    . n*), sum (A - M)^2]``.  ``return_maps``: also ``maps`` fp32
+    ``[F,V,5,H,W]``, the planes opacity, depth, n_x, n_y, n_z; without a table
+    (which needs ``return_maps``) the maps alone.  A (field, view) row does not
+    depend on the rest of the batch; bitwise reproducible.  HIP
+    (``csrc/field_geom.hip``, which states the rule) on the GPU, the float64
+    torch form on the CPU."""
+    F, V, _ = _t.field_geometry_check(grid, K, R, t, H, W, samples=samples, bound=bound, rescale_from=rescale_from,
+                                      table=table, return_maps=return_maps)
+    impl = _h() if F * V > 0 and grid.is_cuda and use_hip(grid, any_dtype=True) else _t
+    return impl.field_geometry(grid, K, R, t, H, W, samples=samples, bound=bound, rescale_from=rescale_from,
+                               table=table, return_maps=return_maps)
+
+
 def psnr(mse):
     """``10 log10(1 / mse)`` on the [0, 1] scale; ``+inf`` where ``mse == 0``."""
     return -10.0 * torch.log10(torch.as_tensor(mse, dtype=torch.float32))
@@ -395,7 +423,7 @@ posenc_nerf = _t.posenc_nerf
 
 __all__ = ["diffusion_inputs", "diff_loss_nhwc", "diff_loss_rows", "loss_bins_add", "group_norm", "gn_film", "conv3x3", "linear", "film_batch", "cat_gn_silu_dense", "cond_conv", "ray_posenc_dir",
            "ray_origin_pe", "ray_conditioning", "attention", "avgpool2", "upsample2",
-           "silu", "logsnr_mlp", "ray_posenc", "image_metrics", "scene_render", "view_consistency", "ensemble_stats", "field_render", "field_loss_grad", "field_batch_loss_grad", "field_adam_tv", "psnr", "posenc_ddpm", "camera_rays", "posenc_nerf", "set_backend",
+           "silu", "logsnr_mlp", "ray_posenc", "image_metrics", "scene_render", "view_consistency", "ensemble_stats", "field_render", "field_loss_grad", "field_batch_loss_grad", "field_adam_tv", "field_geometry", "psnr", "posenc_ddpm", "camera_rays", "posenc_nerf", "set_backend",
            "use_hip", "load_library", "library_error", "lib_path"]
 
 

@@ -142,6 +142,9 @@ SIGNATURES = {
     "d3d_field_fit_loss_grad": [P, P, P, P, P, P, P, P, I, L, I, L, U64, I, I, C.c_double, P],
     "d3d_field_adam_tv": [P, P, P, P, P, I, I, I, C.c_double, C.c_double, C.c_double, C.c_double, C.c_double,
                           C.c_double, C.c_double, P],
+    # field_geom.hip
+    "d3d_field_geometry_blocks": [I, I],
+    "d3d_field_geometry": [P, P, P, P, P, I, I, I, I, I, I, C.c_double, I, P, P, P, P],
 }
 
 

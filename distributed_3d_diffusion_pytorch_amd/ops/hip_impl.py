@@ -3064,3 +3064,30 @@ def field_adam_tv(grid, grid_out, exp_avg, exp_avg_sq, grad, *, step, lr, betas=
     _chk(_lib.d3d_field_adam_tv(grid.data_ptr(), grid_out.data_ptr(), exp_avg.data_ptr(), exp_avg_sq.data_ptr(),
                                 grad.data_ptr(), F, G, int(step), float(lr), float(betas[0]), float(betas[1]),
                                 float(eps), float(grad_scale), float(tv_rgb), float(tv_sigma), _st()), "field_adam_tv")
+
+
+# ------------------------------------------------------- field geometry ---
+def field_geometry(grid, K, R, t, H, W, *, samples, bound=1.0, rescale_from=128, table=None, return_maps=False):
+    """scores fp64 [F,V,7] (with a table) and maps fp32 [F,V,5,H,W] (with
+    ``return_maps``) of F fields under V cameras each (csrc/field_geom.hip: a
+    wave per 8 x 8 pixel tile walks its rays in registers and traces the truth
+    in fp64 from a table staged in LDS; fixed-order block partials and a final
+    sum; bitwise reproducible, no host synchronise).  Graph-capturable."""
+    F, V, G = _t.field_geometry_check(grid, K, R, t, H, W, samples=samples, bound=bound, rescale_from=rescale_from,
+                                      table=table, return_maps=return_maps)
+    K, R, t = K.contiguous(), R.contiguous(), t.contiguous()
+    dev = grid.device
+    maps = torch.empty(F, V, _t.FG_PLANES, H, W, dtype=F32, device=dev) if return_maps else None
+    scores = part = None
+    if table is not None:
+        table = table.contiguous()
+        scores = torch.empty(F, V, _t.FG_ROWS, dtype=torch.float64, device=dev)
+        part = torch.empty(F, V, max(_lib.d3d_field_geometry_blocks(H, W), 0), _t.FG_ROWS, dtype=torch.float64,
+                           device=dev)
+    if F * V > 0:
+        _chk(_lib.d3d_field_geometry(grid.data_ptr(), K.data_ptr(), R.data_ptr(), t.data_ptr(), _ptr(table), F, V, H, W,
+                                     int(samples), G, float(bound), int(rescale_from), _ptr(maps), _ptr(part),
+                                     _ptr(scores), _st()), "field_geometry")
+    if table is None:
+        return maps
+    return (scores, maps) if return_maps else scores

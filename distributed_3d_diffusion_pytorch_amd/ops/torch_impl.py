@@ -862,10 +862,11 @@ def field_check(name, grid, rays_o, rays_d, target=None, *, samples, bound, widt
     return G, R
 
 
-def _field_march(grid, o, d, S: int, bound: float, dt):
-    """C [R,3] on the [0, 1] scale of csrc/field.hip's rule, in ``dt``."""
-    G = grid.shape[0]
-    o, d, flat = o.to(dt), d.to(dt), grid.reshape(-1, 4)
+def _field_cells(G: int, o, d, S: int, bound: float, dt):
+    """The samples of R rays in ``dt``: (hit [R], delta [R], t_i [R,S], the
+    cell's corner (0, 0, 0) i0 [R,S,3] int64 as (ix, iy, iz), the weights
+    toward the +1 corners f [R,S,3])."""
+    o, d = o.to(dt), d.to(dt)
     b = torch.tensor(bound, dtype=dt, device=o.device)
     t0 = torch.zeros_like(o[:, 0])
     t1 = torch.full_like(t0, FIELD_T_MAX)
@@ -884,7 +885,14 @@ def _field_march(grid, o, d, S: int, bound: float, dt):
     pos = o[:, None, :] + ti[..., None] * d[:, None, :]                                          # [R,S,3]
     g = ((pos + b) * torch.tensor((G - 1) / (2.0 * bound), dtype=dt, device=o.device)).clamp(0, G - 1)
     i0 = g.detach().floor().clamp(max=G - 2).long()
-    f = g - i0.to(dt)
+    return hit, delta, ti, i0, g - i0.to(dt)
+
+
+def _field_march(grid, o, d, S: int, bound: float, dt):
+    """C [R,3] on the [0, 1] scale of csrc/field.hip's rule, in ``dt``."""
+    G = grid.shape[0]
+    flat = grid.reshape(-1, 4)
+    hit, delta, ti, i0, f = _field_cells(G, o, d, S, bound, dt)
     v = torch.zeros(*ti.shape, 4, dtype=dt, device=o.device)
     for k in range(8):                     # corner k = (dz, dy, dx), ascending: the kernel's order
         dz, dy, dx = k >> 2, (k >> 1) & 1, k & 1
@@ -897,8 +905,8 @@ def _field_march(grid, o, d, S: int, bound: float, dt):
     sigma = raw.clamp(min=0) + torch.log1p(torch.exp(-raw.abs()))
     rgb = torch.sigmoid(v[..., :3])
     alpha = -torch.expm1(-sigma * delta[:, None])
-    T = torch.ones_like(t0)
-    C = torch.zeros_like(o)
+    T = torch.ones_like(delta)
+    C = torch.zeros(o.shape, dtype=dt, device=o.device)
     for i in range(S):
         C = C + (T * alpha[:, i])[:, None] * rgb[:, i]
         T = T * (1 - alpha[:, i])
@@ -1086,3 +1094,150 @@ def field_adam_tv(grid, grid_out, exp_avg, exp_avg_sq, grad, *, step, lr, betas=
         grid_out.copy_(p)
         exp_avg.copy_(m)
         exp_avg_sq.copy_(v)
+
+
+# ------------------------------------------------------- field geometry ---
+# Opacity, depth and normals of fitted fields along camera rays, and their
+# score against a procedural scene's true surface (csrc/field_geom.hip holds
+# the rule in full).
+FG_ROWS, FG_PLANES = 7, 5            # the score row; the map planes (opacity, depth, n_x, n_y, n_z)
+FG_HIT = 0.5                         # the field "hits" where its opacity is above this
+
+
+def field_geometry_check(grid, K, R, t, H, W, *, samples, bound, rescale_from, table, return_maps):
+    """Argument check shared by both backends (ValueError); returns (F, V, G)."""
+    name = "field_geometry"
+    if not isinstance(grid, torch.Tensor):
+        raise ValueError(f"{name}: grid must be a tensor, got {type(grid).__name__}")
+    _field_tensors(name, (("grid", grid),), grid.device)
+    F, G = _field_batch_grid(name, grid)
+    if not isinstance(R, torch.Tensor) or R.dim() != 4 or tuple(R.shape[2:]) != (3, 3) or R.shape[0] != F:
+        raise ValueError(f"{name}: R must be a tensor [{F},V,3,3], got "
+                         f"{tuple(R.shape) if isinstance(R, torch.Tensor) else type(R).__name__}")
+    V = int(R.shape[1])
+    named = (("K", K, (F, 3, 3)), ("R", R, (F, V, 3, 3)), ("t", t, (F, V, 3)))
+    if table is not None:
+        named += (("table", table, (F, SCENE_SLOTS, SCENE_WORDS)),)
+    for nm, x, shape in named:
+        if not isinstance(x, torch.Tensor):
+            raise ValueError(f"{name}: {nm} must be a tensor, got {type(x).__name__}")
+        if tuple(x.shape) != shape:
+            raise ValueError(f"{name}: {nm} must be {list(shape)} for {F} fields of {V} views, got {tuple(x.shape)}")
+        if x.dtype != torch.float64:
+            raise ValueError(f"{name}: {nm} must be float64, got {x.dtype}")
+        if x.device != grid.device:
+            raise ValueError(f"{name}: {nm} is on {x.device}, the grid on {grid.device}")
+    for nm, v, lo in (("H", H, 1), ("W", W, 1), ("samples", samples, 1), ("rescale_from", rescale_from, 0)):
+        if not _is_int(v) or v < lo:
+            raise ValueError(f"{name}: {nm} must be an integer >= {lo}, got {v!r}")
+    if V > FIELD_MAX_BATCH or H * W >= 1 << 31:
+        raise ValueError(f"{name}: at most {FIELD_MAX_BATCH} views per field and 2^31 - 1 pixels per view, got "
+                         f"{V} views of {H} x {W}")
+    if not (isinstance(bound, (int, float)) and 0.0 < float(bound) < float("inf")):
+        raise ValueError(f"{name}: bound must be a positive finite number, got {bound!r}")
+    if table is None and not return_maps:
+        raise ValueError(f"{name}: without a table there are no scores: pass return_maps=True")
+    return F, V, G
+
+
+def field_geometry(grid, K, R, t, H, W, *, samples, bound=1.0, rescale_from=128, table=None, return_maps=False,
+                   dtype=torch.float64):
+    """scores fp64 [F,V,7] (with a table) and maps fp32 [F,V,5,H,W] (with
+    ``return_maps``): the torch form of csrc/field_geom.hip, which states the
+    rule.  The rays and the truth are float64 whatever ``dtype`` is; the walk
+    through the field -- from the ray rounded to fp32 -- the opacity, depth
+    and normal are evaluated in ``dtype`` (float64: the CPU path and the
+    kernel's oracle)."""
+    return _field_geometry(grid, K, R, t, H, W, samples=samples, bound=bound, rescale_from=rescale_from, table=table,
+                           return_maps=return_maps, dtype=dtype)
+
+
+def _field_geometry(grid, K, R, t, H, W, *, samples, bound, rescale_from, table, return_maps, dtype, cond=None):
+    """:func:`field_geometry`; ``cond`` (a dict) also receives how well a
+    pixel's values are conditioned, each [F,V,H,W] in ``dtype``: ``gnorm``,
+    ``|g|`` before the normalisation; ``face``, the smallest distance in grid
+    units of one of the ray's samples from a cell face, where the gradient
+    jumps; and with a table ``n_true`` [F,V,3,H,W] fp64, the true normals."""
+    F, V, G = field_geometry_check(grid, K, R, t, H, W, samples=samples, bound=bound, rescale_from=rescale_from,
+                                   table=table, return_maps=return_maps)
+    dt, dev, S, bound = torch.float64, grid.device, int(samples), float(bound)
+    ref = float(rescale_from) if rescale_from else None
+    s = torch.tensor([W / ref, H / ref, 1.0] if ref else [1.0, 1.0, 1.0], dtype=dt, device=dev)
+    py, px = torch.meshgrid(torch.arange(H, dtype=dt, device=dev), torch.arange(W, dtype=dt, device=dev),
+                            indexing="ij")
+    scale = torch.tensor((G - 1) / (2.0 * bound), dtype=dtype, device=dev)
+    e = lambda x: x[:, None, None]  # noqa: E731
+    scores = torch.zeros(F, V, FG_ROWS, dtype=dt, device=dev)
+    maps = torch.zeros(F, V, FG_PLANES, H, W, dtype=torch.float32, device=dev)
+    if cond is not None:
+        cond.update(gnorm=torch.zeros(F, V, H, W, dtype=dtype, device=dev),
+                    face=torch.zeros(F, V, H, W, dtype=dtype, device=dev),
+                    n_true=torch.zeros(F, V, 3, H, W, dtype=dt, device=dev))
+    with torch.no_grad():
+        for f in range(F):
+            Kinv = _inv3((K[f] * s[:, None])[None]).expand(V, 3, 3)
+            d = _scene_dirs(Kinv, R[f], px + 0.5, py + 0.5)                        # 3 x [V,H,W] fp64
+            o32 = t[f].float()[:, None, :].expand(V, H * W, 3).reshape(-1, 3)
+            d32 = torch.stack(d, -1).float().reshape(-1, 3)
+            hit, delta, ti, i0, fr = _field_cells(G, o32, d32, S, bound, dtype)
+            sig = grid[f].reshape(-1, 4)[:, 3].to(dtype)
+            raw = torch.zeros_like(ti)
+            gr = [torch.zeros_like(ti) for _ in range(3)]
+            for k in range(8):             # corner k = (dz, dy, dx), ascending: the kernel's order
+                dz, dy, dx = k >> 2, (k >> 1) & 1, k & 1
+                wx = fr[..., 0] if dx else 1 - fr[..., 0]
+                wy = fr[..., 1] if dy else 1 - fr[..., 1]
+                wz = fr[..., 2] if dz else 1 - fr[..., 2]
+                v = sig[((i0[..., 2] + dz) * G + (i0[..., 1] + dy)) * G + (i0[..., 0] + dx)]
+                raw = raw + ((wz * wy) * wx) * v
+                gr[0] = gr[0] + (wz * wy) * (v if dx else -v)
+                gr[1] = gr[1] + (wz * wx) * (v if dy else -v)
+                gr[2] = gr[2] + (wy * wx) * (v if dz else -v)
+            sigma = raw.clamp(min=0) + torch.log1p(torch.exp(-raw.abs()))
+            alpha = -torch.expm1(-sigma * delta[:, None])
+            T = torch.ones_like(delta)
+            A, Dn = torch.zeros_like(delta), torch.zeros_like(delta)
+            g = [torch.zeros_like(delta) for _ in range(3)]
+            for i in range(S):
+                w = T * alpha[:, i]
+                A = A + w
+                Dn = Dn + w * ti[:, i]
+                g = [g[a] + w * (gr[a][:, i] * scale) for a in range(3)]
+                T = T * (1 - alpha[:, i])
+            P = hit & (A > FG_HIT)
+            zero = torch.zeros_like(A)
+            A = torch.where(hit, A, zero)
+            D = torch.where(P, Dn / torch.where(P, A, torch.ones_like(A)), torch.full_like(A, float("inf")))
+            gn = torch.sqrt((g[0] * g[0] + g[1] * g[1]) + g[2] * g[2])
+            ok = P & (gn > 0)
+            n = [torch.where(ok, -g[a] / torch.where(ok, gn, torch.ones_like(gn)), zero) for a in range(3)]
+            planes = [x.reshape(V, H, W) for x in (A, D, *n)]
+            maps[f] = torch.stack(planes, 1).float()
+            if cond is not None:
+                cond["gnorm"][f] = gn.reshape(V, H, W)
+                cond["face"][f] = torch.minimum(fr, 1 - fr).flatten(1).min(1).values.reshape(V, H, W)
+            if table is None:
+                continue
+            prims = _scene_prims(table[f][None].expand(V, SCENE_SLOTS, SCENE_WORDS), t[f])
+            ts, prim, nl, _ = _scene_nearest(prims, d)
+            M = prim >= 0
+            ns = [torch.zeros_like(ts) for _ in range(3)]
+            for p, (Am, _, _, _) in enumerate(prims):                  # n* = normalize(A^T n_local), as scene_shade
+                w = [e(Am[:, 0, k]) * nl[0] + e(Am[:, 1, k]) * nl[1] + e(Am[:, 2, k]) * nl[2] for k in range(3)]
+                wn = torch.sqrt(w[0] * w[0] + w[1] * w[1] + w[2] * w[2])
+                ns = [torch.where(prim == p, w[k] / wn, ns[k]) for k in range(3)]
+            if cond is not None:
+                cond["n_true"][f] = torch.stack(ns, 1)
+            Ad, Dd, nd = planes[0].to(dt), planes[1].to(dt), [x.to(dt) for x in planes[2:]]
+            Pm = P.reshape(V, H, W)
+            both = M & Pm
+            z = torch.zeros_like(ts)
+            df = torch.where(both, Dd - torch.where(both, ts, z), z)
+            cos = (nd[0] * ns[0] + nd[1] * ns[1]) + nd[2] * ns[2]
+            sil = Ad - M.to(dt)
+            for k, q in enumerate((M.to(dt), Pm.to(dt), both.to(dt), df.abs(), df * df,
+                                   torch.where(both, 1.0 - cos, z), sil * sil)):
+                scores[f, :, k] = q.flatten(1).sum(1)
+    if table is None:
+        return maps
+    return (scores, maps) if return_maps else scores

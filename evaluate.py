@@ -81,6 +81,10 @@ def parse(argv=None):
                     help="--field_holdout: weight of the smoothness term on the grid (colour and density alike); "
                          "not 0 fits through engine.fit_fields (profiles/field/README.md recommends a value)")
     ap.add_argument("--timesteps", type=int, default=256)
+    ap.add_argument("--field_geometry", action="store_true",
+                    help="--field_holdout with --procedural: also read depth, silhouette and normals out of every "
+                         "fitted field at the held-out poses (ops.field_geometry) and score them against the scenes' "
+                         "true surface; the field block's rows, per_w and gt_field get the geom_* fields")
     ap.add_argument("--sampler", default="ancestral", choices=["ancestral", "ddim", "dpmpp2m"],
                     help="update rule: the 256-step ancestral chain, DDIM or DPM-Solver++(2M) for few steps")
     ap.add_argument("--eta", type=float, default=0.0, help="DDIM noise level in [0, 1] (1 = ancestral variance)")
@@ -156,6 +160,9 @@ def run(args) -> dict:
 
     if args.consistency and not args.procedural:
         raise ValueError("--consistency needs --procedural: SRN data carries no geometry to score against")
+    if args.field_geometry and not (args.procedural and args.field_holdout):
+        raise ValueError("--field_geometry needs --procedural and --field_holdout: it scores the fitted fields against "
+                         "the scenes' geometry, which SRN data does not carry")
     if args.backend != "auto":
         ops.set_backend(args.backend)
     dev = torch.device("cuda", 0) if torch.cuda.is_available() else torch.device("cpu")
@@ -222,7 +229,8 @@ def run(args) -> dict:
         from distributed_3d_diffusion_pytorch_amd.engine import field_rows, summarize_field
         hold = [int(v) for v in args.field_holdout.split(",")]
         fit = {"grid": args.field_grid, "seed": args.seed, **({"iters": args.field_iters} if args.field_iters else {}),
-               "batch": args.field_batch, "tv_rgb": args.field_tv, "tv_sigma": args.field_tv}
+               "batch": args.field_batch, "tv_rgb": args.field_tv, "tv_sigma": args.field_tv,
+               **({"geometry": True} if args.field_geometry else {})}
         frows = field_rows(objects, kept, views, hold, w, dev, **fit)
         result["field"] = {"per_w": summarize_field(frows), "rows": frows}
         if args.procedural:
