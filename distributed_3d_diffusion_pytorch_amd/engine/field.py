@@ -159,6 +159,43 @@ def _geometry(grids, scenes, R, t, K, H: int, W: int, fit) -> List[dict]:
     return [_geom_fields(row, V * H * W) for row in scores.sum(1).cpu().tolist()]
 
 
+# Chosen on procedural ground-truth views at 64 x 64 (profiles/field/README.md holds the sweep).
+REPROJ_TOL = 0.05
+REPROJ_KEYS = ("reproj_n_covisible", "reproj_n_clean", "reproj_mse", "reproj_psnr", "reproj_covis_mse",
+               "reproj_covis_psnr", "reproj_depth_mae")
+
+
+def _reproj_fields(sums: Sequence[float]) -> dict:
+    """The ``reproj_*`` fields of pooled ``ops.depth_consistency`` rows: ``sums``
+    the 7 sums over all their ordered view pairs.  Every value is sum / count,
+    None where its count is 0; a zero error counts with 100 dB, as in
+    ``field_psnr``."""
+    ncov, ncl = int(round(sums[2])), int(round(sums[3]))
+    mse, cmse = (sums[5] / (3 * ncl) if ncl else None), (sums[4] / (3 * ncov) if ncov else None)
+    db = lambda m: None if m is None else 10.0 * math.log10(1.0 / m) if m > 0 else 100.0  # noqa: E731
+    return {"reproj_n_covisible": ncov, "reproj_n_clean": ncl, "reproj_mse": mse, "reproj_psnr": db(mse),
+            "reproj_covis_mse": cmse, "reproj_covis_psnr": db(cmse),
+            "reproj_depth_mae": sums[6] / ncl if ncl else None, "reproj_sums": [float(x) for x in sums]}
+
+
+def _reproj(grids, images, R, t, K, fit, tol: float) -> List[dict]:
+    """The ``reproj_*`` fields of F fitted ``grids`` [F,G,G,G,4] and the views
+    ``images`` [F,V,3,H,W] they belong to, training and held-out, under the
+    cameras ``R`` [F,V,3,3], ``t`` [F,V,3]: one ``ops.field_geometry`` call
+    reads the fields' depth at all V poses, one ``ops.depth_consistency`` call
+    scores the V (V - 1) ordered pairs of every field under those depths."""
+    F, V, _, H, W = (int(s) for s in images.shape)
+    dev = grids.device
+    Kf = K.to(dev).double()[None].expand(F, 3, 3).contiguous()
+    Rd, td = R.to(dev).double().contiguous(), t.to(dev).double().contiguous()
+    ref = fit.get("rescale_from", 128)
+    maps = ops.field_geometry(grids.contiguous(), Kf, Rd, td, H, W, samples=fit.get("samples", 64),
+                              bound=fit.get("bound", 1.0), rescale_from=ref, return_maps=True)
+    stats = ops.depth_consistency(maps[:, :, 1].contiguous(), images.to(dev).float().contiguous(), Kf, Rd, td, tol=tol,
+                                  rescale_from=ref)
+    return [_reproj_fields(row) for row in stats.sum((1, 2)).cpu().tolist()]
+
+
 def _need_scene(scene, name: str):
     if scene is None:
         raise ValueError(f"geometry needs the object's scene table (procedural objects carry one); {name} has none")
@@ -182,7 +219,7 @@ def _batched(batch: int, tv_rgb: float, tv_sigma: float) -> bool:
 
 def field_consistency(images, R, t, K, train: Sequence[int], test: Sequence[int], *, batch: int = 1,
                       tv_rgb: float = 0.0, tv_sigma: float = 0.0, geometry: bool = False, scene=None,
-                      **fit) -> dict:
+                      reproj: bool = False, reproj_tol: float = REPROJ_TOL, **fit) -> dict:
     """The score of one set of views: fit a field (:func:`fit_field`, ``fit``
     its keywords) to ``images[train]``, render the poses of ``test`` and score
     the renders against ``images[test]`` with ``ops.image_metrics`` (as 8-bit
@@ -199,8 +236,17 @@ def field_consistency(images, R, t, K, train: Sequence[int], test: Sequence[int]
     ``geom_depth_rmse`` and ``geom_normal_cos`` over the pixels both hit and
     ``geom_sil_mse``, each pooled over the held-out views as sum / count (None
     where the count is 0; ``geom_sums`` / ``geom_pixels`` keep the sums for
-    further pooling).  Fewer than 3 training views, or no test view, is a
-    ValueError."""
+    further pooling).  ``reproj``: the fitted field's depth is read at the poses
+    of ALL views (``ops.field_geometry``) and the views themselves are warped
+    into each other under it (``ops.depth_consistency`` with ``tol =
+    reproj_tol``), so appearance never goes through the grid; the row gains,
+    pooled over the V (V - 1) ordered pairs as sum / count (None at count 0),
+    ``reproj_n_covisible`` / ``reproj_n_clean``, ``reproj_mse`` /
+    ``reproj_psnr`` over the clean pixels (the [0, 1] scale of
+    ``ops.image_metrics``, unquantized), ``reproj_covis_mse`` /
+    ``reproj_covis_psnr`` over all co-visible pixels, ``reproj_depth_mae`` (the
+    fields' own depth disagreement at the clean pixels) and ``reproj_sums``.
+    Fewer than 3 training views, or no test view, is a ValueError."""
     train, test = _split(train, test)
     if geometry:
         _need_scene(scene, "the object")
@@ -214,12 +260,14 @@ def field_consistency(images, R, t, K, train: Sequence[int], test: Sequence[int]
     if geometry:
         H, W = (int(s) for s in images.shape[-2:])
         row.update(_geometry(grid[None], scene[None], R[test][None], t[test][None], K, H, W, fit)[0])
+    if reproj:
+        row.update(_reproj(grid[None], images[None], R[None], t[None], K, fit, reproj_tol)[0])
     return row
 
 
 def field_rows(objects, images: Dict[tuple, torch.Tensor], views: Sequence[int], holdout: Sequence[int],
                w: Sequence[float], device=None, *, batch: int = 1, tv_rgb: float = 0.0, tv_sigma: float = 0.0,
-               geometry: bool = False, **fit) -> List[dict]:
+               geometry: bool = False, reproj: bool = False, reproj_tol: float = REPROJ_TOL, **fit) -> List[dict]:
     """One :func:`field_consistency` row per (object, guidance weight) of an
     ``evaluate_objects(..., keep_images=True)`` run: ``images[(instance, view)]``
     the generated ``[len(w),3,H,W]`` batch; the views in ``holdout`` are held
@@ -231,7 +279,10 @@ def field_rows(objects, images: Dict[tuple, torch.Tensor], views: Sequence[int],
     ``geometry``: every row also gets the ``geom_*`` fields of
     :func:`field_consistency` against the object's ``scene`` (ValueError for
     an object without one); the batched path reads all grids of a
-    ``fit_fields`` call out in one ``ops.field_geometry`` call."""
+    ``fit_fields`` call out in one ``ops.field_geometry`` call.  ``reproj``:
+    every row also gets the ``reproj_*`` fields of :func:`field_consistency`;
+    the batched path makes one ``ops.field_geometry`` and one
+    ``ops.depth_consistency`` call per ``fit_fields`` call."""
     views, holdout = [int(v) for v in views], [int(v) for v in holdout]
     bad = [v for v in holdout if v not in views]
     if bad or len(set(holdout)) != len(holdout):
@@ -254,6 +305,10 @@ def field_rows(objects, images: Dict[tuple, torch.Tensor], views: Sequence[int],
             H, W = (int(s) for s in todo[0][2].shape[-2:])
             geom = _geometry(grids, torch.stack([p[6] for p in todo]), torch.stack([p[3][te] for p in todo]),
                              torch.stack([p[4][te] for p in todo]), todo[0][5], H, W, fit)
+        if reproj:
+            rp = _reproj(grids, torch.stack([p[2] for p in todo]), torch.stack([p[3] for p in todo]),
+                         torch.stack([p[4] for p in todo]), todo[0][5], fit, reproj_tol)
+            geom = [{**g, **r} for g, r in zip(geom, rp)]
         for f, (name, wv, img, R, t, K, _) in enumerate(todo):
             rows.append({"instance": name, "w": wv, **_score(grids[f], last[f], img, R, t, K, tr, te, fit), **geom[f]})
         todo.clear()
@@ -268,7 +323,7 @@ def field_rows(objects, images: Dict[tuple, torch.Tensor], views: Sequence[int],
             if not batched:
                 rows.append({"instance": o.name, "w": wv,
                              **field_consistency(img.float(), R, t, o.K.to(dev), train, test, geometry=geometry,
-                                                 scene=scene, **fit)})
+                                                 scene=scene, reproj=reproj, reproj_tol=reproj_tol, **fit)})
                 continue
             K = o.K.to(dev)
             if todo and (len(todo) == batch or not torch.equal(K, todo[0][5])):     # one K per fit_fields call
@@ -282,7 +337,8 @@ def field_rows(objects, images: Dict[tuple, torch.Tensor], views: Sequence[int],
 def summarize_field(rows: Sequence[dict]) -> dict:
     """Per guidance weight (``"gt"`` for the ground-truth rows) the means of
     ``field_psnr``, ``field_ssim`` and ``fit_loss`` over the objects; for rows
-    with ``geom_*`` fields also those, pooled over the objects as sum / count."""
+    with ``geom_*`` / ``reproj_*`` fields also those, pooled over the objects as
+    sum / count."""
     out = {}
     for wv in sorted({r["w"] for r in rows}, key=lambda x: -math.inf if x is None else x):
         sel = [r for r in rows if r["w"] == wv]
@@ -291,5 +347,8 @@ def summarize_field(rows: Sequence[dict]) -> dict:
             pooled = _geom_fields([sum(r["geom_sums"][k] for r in sel) for k in range(7)],
                                   sum(r["geom_pixels"] for r in sel))
             d.update({k: pooled[k] for k in GEOM_KEYS})
+        if sel and all("reproj_sums" in r for r in sel):
+            pooled = _reproj_fields([sum(r["reproj_sums"][k] for r in sel) for k in range(7)])
+            d.update({k: pooled[k] for k in REPROJ_KEYS})
         out["gt" if wv is None else f"{wv:g}"] = d
     return out

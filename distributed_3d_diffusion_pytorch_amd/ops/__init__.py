@@ -412,6 +412,35 @@ def field_geometry(grid, K, R, t, H: int, W: int, *, samples: int, bound: float 
                                table=table, return_maps=return_maps)
 
 
+def depth_consistency(depth, images, K, R, t, *, tol: float, rescale_from: int = 128, return_class: bool = False):
+    """How well the V views of an object agree under per-view depths, for all
+    ordered pairs (target a, source b): ``depth`` fp32 ``[F,V,H,W]``, the
+    distance along the unit pixel-centre ray, ``+inf`` where a view sees no
+    surface (plane 1 of :func:`field_geometry`'s maps, the depth aux of
+    :func:`scene_render`); ``images`` fp32 ``[F,V,3,H,W]`` in [-1, 1]; ``K``
+    fp64 ``[F,3,3]`` (the intrinsics of the ``rescale_from``-pixel image; 0: of
+    this size), ``R`` fp64 ``[F,V,3,3]`` cam-to-world, ``t`` fp64 ``[F,V,3]``;
+    at most 64 views.  A target pixel with a finite depth is lifted to its
+    point, projected into view b and compared with b's depth there: within
+    ``tol`` (relative to the distance from b's camera; required, > 0) at the
+    nearest tap it is co-visible (class 2), else hidden (1); co-visible pixels
+    whose four source taps and whose target neighbours also lie within ``tol``
+    are clean (3); pixels without depth are background (0).  Returns ``stats``
+    fp64 ``[F,V,V,7]``, index ``[f,a,b]``: ``[n_background, n_hidden,
+    n_covisible (clean included), n_clean, sum_covisible ((tgt - warp) / 2)^2
+    over the 3 channels, the same over clean pixels, sum_clean |dist -
+    qbar|]``, ``warp`` / ``qbar`` the bilinear samples of b's image / depth
+    (``mse = sum / (3 n)``); rows ``[f,a,a]`` are zero.  ``return_class``: also
+    the class planes int32 ``[F,V,V,H,W]``, -1 on the diagonal.  A field's rows
+    do not depend on the rest of the batch; bitwise reproducible.  HIP
+    (``csrc/depth_consistency.hip``, which states the rule) on the GPU, the
+    float64 torch form on the CPU."""
+    F, _, _, _ = _t.depth_consistency_check(depth, images, K, R, t, tol=tol, rescale_from=rescale_from)
+    impl = _h() if F > 0 and depth.is_cuda and use_hip(depth, any_dtype=True) else _t
+    return impl.depth_consistency(depth, images, K, R, t, tol=tol, rescale_from=rescale_from,
+                                  return_class=return_class)
+
+
 def psnr(mse):
     """``10 log10(1 / mse)`` on the [0, 1] scale; ``+inf`` where ``mse == 0``."""
     return -10.0 * torch.log10(torch.as_tensor(mse, dtype=torch.float32))
@@ -423,7 +452,7 @@ posenc_nerf = _t.posenc_nerf
 
 __all__ = ["diffusion_inputs", "diff_loss_nhwc", "diff_loss_rows", "loss_bins_add", "group_norm", "gn_film", "conv3x3", "linear", "film_batch", "cat_gn_silu_dense", "cond_conv", "ray_posenc_dir",
            "ray_origin_pe", "ray_conditioning", "attention", "avgpool2", "upsample2",
-           "silu", "logsnr_mlp", "ray_posenc", "image_metrics", "scene_render", "view_consistency", "ensemble_stats", "field_render", "field_loss_grad", "field_batch_loss_grad", "field_adam_tv", "field_geometry", "psnr", "posenc_ddpm", "camera_rays", "posenc_nerf", "set_backend",
+           "silu", "logsnr_mlp", "ray_posenc", "image_metrics", "scene_render", "view_consistency", "ensemble_stats", "field_render", "field_loss_grad", "field_batch_loss_grad", "field_adam_tv", "field_geometry", "depth_consistency", "psnr", "posenc_ddpm", "camera_rays", "posenc_nerf", "set_backend",
            "use_hip", "load_library", "library_error", "lib_path"]
 
 

@@ -145,6 +145,9 @@ SIGNATURES = {
     # field_geom.hip
     "d3d_field_geometry_blocks": [I, I],
     "d3d_field_geometry": [P, P, P, P, P, I, I, I, I, I, I, C.c_double, I, P, P, P, P],
+    # depth_consistency.hip
+    "d3d_depth_consistency_blocks": [I, I],
+    "d3d_depth_consistency": [P, P, P, P, P, I, I, I, I, C.c_double, I, P, P, P, P],
 }
 
 

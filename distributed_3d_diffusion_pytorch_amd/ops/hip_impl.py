@@ -3091,3 +3091,24 @@ def field_geometry(grid, K, R, t, H, W, *, samples, bound=1.0, rescale_from=128,
     if table is None:
         return maps
     return (scores, maps) if return_maps else scores
+
+
+# ----------------------------------------------- depth reprojection score ---
+def depth_consistency(depth, images, K, R, t, *, tol, rescale_from=128, return_class=False):
+    """stats fp64 [F,V,V,7] (and, with ``return_class``, the class planes int32
+    [F,V,V,H,W]) of the ordered view pairs of F objects
+    (csrc/depth_consistency.hip: a wave per 8 x 8 target tile keeps the lifted
+    point in registers over the loop of sources, whose projections sit in LDS;
+    ballot counts and fixed-order fp64 sums, block partials and a final sum;
+    bitwise reproducible, no host synchronise).  Graph-capturable."""
+    F, V, H, W = _t.depth_consistency_check(depth, images, K, R, t, tol=tol, rescale_from=rescale_from)
+    dev = depth.device
+    stats = torch.empty(F, V, V, _t.DC_STATS, dtype=torch.float64, device=dev)
+    cls = torch.empty(F, V, V, H, W, dtype=torch.int32, device=dev) if return_class else None
+    part = torch.empty(F, V, V, max(_lib.d3d_depth_consistency_blocks(H, W), 0), _t.DC_STATS, dtype=torch.float64,
+                       device=dev)
+    if F > 0:
+        _chk(_lib.d3d_depth_consistency(depth.data_ptr(), images.data_ptr(), K.data_ptr(), R.data_ptr(), t.data_ptr(),
+                                        F, V, H, W, float(tol), int(rescale_from), part.data_ptr(), stats.data_ptr(),
+                                        _ptr(cls), _st()), "depth_consistency")
+    return (stats, cls) if return_class else stats

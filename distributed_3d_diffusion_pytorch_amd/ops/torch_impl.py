@@ -1241,3 +1241,138 @@ def _field_geometry(grid, K, R, t, H, W, *, samples, bound, rescale_from, table,
     if table is None:
         return maps
     return (scores, maps) if return_maps else scores
+
+
+# ------------------------------------------------ depth reprojection score ---
+# Consistency between the views of one object under per-view depth planes
+# (csrc/depth_consistency.hip holds the rule in full).
+DC_STATS, DC_MAX_VIEWS = 7, 64
+
+
+def depth_consistency_check(depth, images, K, R, t, *, tol, rescale_from):
+    """Argument check shared by both backends (ValueError); returns (F, V, H, W)."""
+    name = "depth_consistency"
+    for nm, x in (("depth", depth), ("images", images), ("K", K), ("R", R), ("t", t)):
+        if not isinstance(x, torch.Tensor):
+            raise ValueError(f"{name}: {nm} must be a tensor, got {type(x).__name__}")
+        if x.device != depth.device:
+            raise ValueError(f"{name}: {nm} is on {x.device}, the depth on {depth.device}")
+        if not x.is_contiguous():
+            raise ValueError(f"{name}: {nm} must be contiguous")
+    if depth.dim() != 4 or min(depth.shape[1:]) < 1:
+        raise ValueError(f"{name}: depth must be [F,V,H,W] with V, H, W >= 1, got {tuple(depth.shape)}")
+    F, V, H, W = (int(s) for s in depth.shape)
+    for nm, x, shape, dtype in (("depth", depth, (F, V, H, W), torch.float32),
+                                ("images", images, (F, V, 3, H, W), torch.float32), ("K", K, (F, 3, 3), torch.float64),
+                                ("R", R, (F, V, 3, 3), torch.float64), ("t", t, (F, V, 3), torch.float64)):
+        if tuple(x.shape) != shape:
+            raise ValueError(f"{name}: {nm} must be {list(shape)} like the depth, got {tuple(x.shape)}")
+        if x.dtype != dtype:
+            raise ValueError(f"{name}: {nm} must be {dtype}, got {x.dtype}")
+    if V > DC_MAX_VIEWS or H * W >= 1 << 31:
+        raise ValueError(f"{name}: at most {DC_MAX_VIEWS} views per field and 2^31 - 1 pixels per view, got {V} views "
+                         f"of {H} x {W}")
+    if isinstance(tol, bool) or not isinstance(tol, (int, float)) or not 0.0 < float(tol) < float("inf"):
+        raise ValueError(f"{name}: tol must be a positive finite number, got {tol!r}")
+    if not _is_int(rescale_from) or rescale_from < 0:
+        raise ValueError(f"{name}: rescale_from must be an integer >= 0, got {rescale_from!r}")
+    return F, V, H, W
+
+
+def depth_consistency(depth, images, K, R, t, *, tol, rescale_from=128, return_class=False):
+    """stats fp64 [F,V,V,7] (and, with ``return_class``, the class planes
+    [F,V,V,H,W] int32: 0 background, 1 hidden, 2 co-visible, 3 clean, -1 on the
+    diagonal) of the ordered view pairs [f, target, source]: the float64 torch
+    form of csrc/depth_consistency.hip, which states the rule.  The CPU path
+    and the kernel's oracle."""
+    return _depth_consistency(depth, images, K, R, t, tol=tol, rescale_from=rescale_from, return_class=return_class)
+
+
+def _depth_consistency(depth, images, K, R, t, *, tol, rescale_from, return_class, cond=None):
+    """:func:`depth_consistency`; ``cond`` (a dict) also receives ``margin``,
+    the smallest relative distance of one of the rule's decisions from its
+    threshold over all pixels where that decision is taken: the ``tol`` tests
+    (of q_n, of the q_k of co-visible pixels, of the neighbour depths) against
+    ``tol dist`` / ``tol D``, the ``floor`` arguments against the nearest
+    integer, ``fx`` / ``fy`` against 1/2 and ``c_z`` against 0 (over dist)."""
+    F, V, H, W = depth_consistency_check(depth, images, K, R, t, tol=tol, rescale_from=rescale_from)
+    dt, dev, tol = torch.float64, depth.device, float(tol)
+    ref = float(rescale_from) if rescale_from else None
+    s = torch.tensor([W / ref, H / ref, 1.0] if ref else [1.0, 1.0, 1.0], dtype=dt, device=dev)
+    py, px = torch.meshgrid(torch.arange(H, dtype=dt, device=dev), torch.arange(W, dtype=dt, device=dev),
+                            indexing="ij")
+    stats = torch.zeros(F, V, V, DC_STATS, dtype=dt, device=dev)
+    cls = torch.full((F, V, V, H, W), -1, dtype=torch.int32, device=dev)
+    margin = [float("inf")]
+
+    def near(x, mask):                           # the decisions' distances from their thresholds
+        if cond is not None and bool(mask.any()):
+            margin[0] = min(margin[0], float(x[mask].abs().min()))
+
+    off = ~torch.eye(V, dtype=torch.bool, device=dev)[:, :, None, None]
+    src = lambda x: x[None, :, None, None]       # noqa: E731  per source view
+    for f in range(F):
+        Ks = K[f] * s[:, None]
+        d = _scene_dirs(_inv3(Ks[None]).expand(V, 3, 3), R[f], px + 0.5, py + 0.5)         # 3 x [V,H,W]
+        Dp = depth[f].to(dt)
+        hit = torch.isfinite(Dp)
+        D = torch.where(hit, Dp, torch.zeros_like(Dp))           # (a miss: any finite point; masked below)
+        X = [t[f, :, k, None, None] + D * d[k] for k in range(3)]
+        smooth = torch.ones_like(hit)
+        lo, hi, al = slice(None, -1), slice(1, None), slice(None)
+        for sl_p, sl_n in (((..., hi), (..., lo)), ((..., lo), (..., hi)),             # the pixel, its neighbour
+                           ((..., hi, al), (..., lo, al)), ((..., lo, al), (..., hi, al))):
+            fin, dn, lim = hit[sl_n], (Dp[sl_n] - D[sl_p]).abs(), tol * D[sl_p]
+            smooth[sl_p] &= fin & (dn <= lim)
+            near((dn - lim) / lim, hit[sl_p] & fin)
+        P = [[Ks[i, 0] * R[f, :, j, 0] + Ks[i, 1] * R[f, :, j, 1] + Ks[i, 2] * R[f, :, j, 2] for j in range(3)]
+             for i in range(3)]                                   # P_b = Ks R_b^T, [V] each
+        e = [X[k][:, None] - src(t[f, :, k]) for k in range(3)]  # [Va,Vb,H,W]
+        dist = torch.sqrt(e[0] * e[0] + e[1] * e[1] + e[2] * e[2])
+        cz = src(R[f, :, 0, 2]) * e[0] + src(R[f, :, 1, 2]) * e[1] + src(R[f, :, 2, 2]) * e[2]
+        kc = [src(P[i][0]) * e[0] + src(P[i][1]) * e[1] + src(P[i][2]) * e[2] for i in range(3)]
+        u, v = kc[0] / kc[2], kc[1] / kc[2]
+        x0, y0 = torch.floor(u - 0.5), torch.floor(v - 0.5)
+        inside = (x0 >= 0.0) & (x0 + 1.0 <= float(W - 1)) & (y0 >= 0.0) & (y0 + 1.0 <= float(H - 1))
+        seen = hit[:, None] & off & (cz > 0.0) & inside
+        zero = torch.zeros_like(u)
+        near(cz / dist, (hit[:, None] & off).expand_as(cz))
+        front = hit[:, None] & off & (cz > 0.0)
+        for w_ in (u - 0.5, v - 0.5):
+            near((w_ - torch.round(w_)) / w_.abs().clamp_min(1.0), front & torch.isfinite(w_))
+        x0, y0 = torch.where(seen, x0, zero), torch.where(seen, y0, zero)      # (elsewhere possibly NaN or outside)
+        fx, fy = torch.where(seen, (u - 0.5) - x0, zero), torch.where(seen, (v - 0.5) - y0, zero)
+        near(fx - 0.5, seen)
+        near(fy - 0.5, seen)
+        base = (torch.arange(V, device=dev) * (H * W))[None, :, None, None] + y0.long() * W + x0.long()
+        take = lambda plane, dy, dx: plane[(base + (dy * W + dx)).clamp(0, V * H * W - 1)]   # noqa: E731
+        dflat = Dp.reshape(-1)
+        q = [take(dflat, 0, 0), take(dflat, 0, 1), take(dflat, 1, 0), take(dflat, 1, 1)]
+        qn = torch.where(fy >= 0.5, torch.where(fx >= 0.5, q[3], q[2]), torch.where(fx >= 0.5, q[1], q[0]))
+        lim = tol * dist
+        ok = lambda x: torch.isfinite(x) & ((dist - x).abs() <= lim)           # noqa: E731
+        cov = seen & ok(qn)
+        near(((dist - qn).abs() - lim) / lim, seen & torch.isfinite(qn))
+        clean = cov & smooth[:, None]
+        for x in q:
+            clean = clean & ok(x)
+            near(((dist - x).abs() - lim) / lim, cov & torch.isfinite(x))
+        w00, w01, w10, w11 = (1.0 - fx) * (1.0 - fy), fx * (1.0 - fy), (1.0 - fx) * fy, fx * fy
+        se = torch.zeros_like(u)
+        for c in range(3):
+            plane = images[f, :, c].to(dt).reshape(-1)
+            warp = w00 * take(plane, 0, 0) + w01 * take(plane, 0, 1) + w10 * take(plane, 1, 0) + w11 * take(plane, 1, 1)
+            r = (images[f, :, c].to(dt)[:, None] - warp) * 0.5
+            se = se + r * r
+        qbar = w00 * q[0] + w01 * q[1] + w10 * q[2] + w11 * q[3]
+        bg, hid = (~hit)[:, None] & off, hit[:, None] & off & ~cov
+        for k, m in enumerate((bg, hid, cov, clean)):
+            stats[f, :, :, k] = m.flatten(2).sum(2).to(dt)
+        stats[f, :, :, 4] = torch.where(cov, se, zero).flatten(2).sum(2)
+        stats[f, :, :, 5] = torch.where(clean, se, zero).flatten(2).sum(2)
+        stats[f, :, :, 6] = torch.where(clean, (dist - qbar).abs(), zero).flatten(2).sum(2)
+        klass = (hit[:, None] & off).to(torch.int32) + cov.to(torch.int32) + clean.to(torch.int32)
+        cls[f] = torch.where(off.expand_as(klass), klass, cls[f])
+    if cond is not None:
+        cond["margin"] = margin[0]
+    return (stats, cls) if return_class else stats

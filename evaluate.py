@@ -85,6 +85,13 @@ def parse(argv=None):
                     help="--field_holdout with --procedural: also read depth, silhouette and normals out of every "
                          "fitted field at the held-out poses (ops.field_geometry) and score them against the scenes' "
                          "true surface; the field block's rows, per_w and gt_field get the geom_* fields")
+    ap.add_argument("--field_reproj", action="store_true",
+                    help="--field_holdout: also read every fitted field's depth at the poses of all generated views and "
+                         "warp the generated views into each other under it (ops.depth_consistency); the field block's "
+                         "rows, per_w and gt_field get the reproj_* fields.  Needs only poses: works on SRN data")
+    ap.add_argument("--field_reproj_tol", type=float, default=None,
+                    help="--field_reproj: relative depth tolerance of a co-visible pixel (default: the engine's, "
+                         "chosen in profiles/field/README.md)")
     ap.add_argument("--sampler", default="ancestral", choices=["ancestral", "ddim", "dpmpp2m"],
                     help="update rule: the 256-step ancestral chain, DDIM or DPM-Solver++(2M) for few steps")
     ap.add_argument("--eta", type=float, default=0.0, help="DDIM noise level in [0, 1] (1 = ancestral variance)")
@@ -163,6 +170,15 @@ def run(args) -> dict:
     if args.field_geometry and not (args.procedural and args.field_holdout):
         raise ValueError("--field_geometry needs --procedural and --field_holdout: it scores the fitted fields against "
                          "the scenes' geometry, which SRN data does not carry")
+    if args.field_reproj:
+        from distributed_3d_diffusion_pytorch_amd.engine.field import REPROJ_TOL
+        if not args.field_holdout:
+            raise ValueError("--field_reproj needs --field_holdout: it scores the generated views under the depth of the "
+                             "field fitted to them")
+        if args.field_reproj_tol is None:
+            args.field_reproj_tol = REPROJ_TOL
+        if not 0.0 < args.field_reproj_tol < float("inf"):
+            raise ValueError(f"--field_reproj_tol must be positive, got {args.field_reproj_tol}")
     if args.backend != "auto":
         ops.set_backend(args.backend)
     dev = torch.device("cuda", 0) if torch.cuda.is_available() else torch.device("cpu")
@@ -230,7 +246,8 @@ def run(args) -> dict:
         hold = [int(v) for v in args.field_holdout.split(",")]
         fit = {"grid": args.field_grid, "seed": args.seed, **({"iters": args.field_iters} if args.field_iters else {}),
                "batch": args.field_batch, "tv_rgb": args.field_tv, "tv_sigma": args.field_tv,
-               **({"geometry": True} if args.field_geometry else {})}
+               **({"geometry": True} if args.field_geometry else {}),
+               **({"reproj": True, "reproj_tol": args.field_reproj_tol} if args.field_reproj else {})}
         frows = field_rows(objects, kept, views, hold, w, dev, **fit)
         result["field"] = {"per_w": summarize_field(frows), "rows": frows}
         if args.procedural:
@@ -279,6 +296,14 @@ def run(args) -> dict:
             d = result["field"]["gt_field"]
             print(f"[evaluate] ground-truth ceiling: field PSNR {d['field_psnr']:.3f} dB  SSIM "
                   f"{d['field_ssim']:.4f}", flush=True)
+        if args.field_reproj:
+            rp = lambda d: ("n/a" if d["reproj_psnr"] is None else f"{d['reproj_psnr']:.3f} dB") + \
+                f" ({d['reproj_n_clean']} clean px)"  # noqa: E731
+            for k, d in sorted(result["field"]["per_w"].items(), key=lambda kv: float(kv[0])):
+                print(f"[evaluate] w={k}: reprojection PSNR under the field's depth {rp(d)}", flush=True)
+            if args.procedural:
+                print(f"[evaluate] ground-truth ceiling: reprojection PSNR under the field's depth "
+                      f"{rp(result['field']['gt_field'])}", flush=True)
     print(f"[evaluate] {result['n_images']} images ({result['n_identical']} identical) in "
           f"{result['wall_seconds']:.2f}s -> {os.path.join(args.out, 'metrics.json')}", flush=True)
     return result

@@ -27,7 +27,7 @@ ARCH = os.environ.get("D3D_OFFLOAD_ARCH", "gfx950")
 # (no packed fp32 add / mul / fma forms in the accumulator rescales).
 _NO_PK_F32 = ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]
 FILE_FLAGS = {"attention_hd.hip": _NO_PK_F32, "field.hip": _NO_PK_F32, "field_fit.hip": _NO_PK_F32,
-              "field_geom.hip": _NO_PK_F32}
+              "field_geom.hip": _NO_PK_F32, "depth_consistency.hip": _NO_PK_F32}
 
 
 def hipcc() -> str:
