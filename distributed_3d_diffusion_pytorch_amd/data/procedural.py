@@ -25,90 +25,64 @@ The rule (everything float64):
 * the image: see ``ops.scene_render``.
 
 Split: object ids with ``o % 10 == 9`` are held out (``split="val"``).
+
+On a HIP device a batch (``ProceduralBatches``) and a list of views
+(``render_views``, ``procedural_objects``) are one fused launch each,
+``ops.procedural_batch`` / ``ops.procedural_render`` (``csrc/procedural.hip``:
+draw, tables, poses and render in one kernel); ``D3D_PROC_FUSED=0`` keeps the
+torch composition of the rule's functions in front of ``ops.scene_render``,
+which is also the CPU path.
 """
 from __future__ import annotations
 
 import json
-import math
 import os
 import pickle
-from typing import Dict, List, Sequence, Tuple
+from typing import Dict, List, Sequence
 
 import numpy as np
 import torch
 
 from .. import ops
-from ..ops.torch_impl import hash_u32, u01, GOLDEN
-from .synthetic import SRN_FOCAL_128, SRN_RADIUS, orbit_look_at
+from ..ops import torch_impl as _t
+from ..ops.torch_impl import (hash_u32, u01, GOLDEN, SRN_FOCAL_128, SRN_RADIUS, orbit_look_at,  # noqa: F401
+                              procedural_scene, procedural_pose, split_object, srn_intrinsics)
 
-P_MAX = 6
-MAX_VIEWS = 4096                     # views of one object (the pose counter's stride)
-MAX_OBJECTS = 1 << 31
-_K_COUNT = 0x5BD1E995
-_K_POSE = 0x7F4A7C15
-_K_BATCH = 0x70726F6365647572        # "procedur": keeps the batch draw apart from the scene and pose draws
+# The rule's pure functions (procedural_scene, procedural_pose, split_object,
+# the batch draw) live in ops.torch_impl, next to the renderer they feed: they
+# are the CPU form of ops.procedural_render / ops.procedural_batch.
+P_MAX = _t.SCENE_SLOTS
+MAX_VIEWS = _t.PROC_MAX_VIEWS        # views of one object (the pose counter's stride)
+MAX_OBJECTS = _t.PROC_MAX_OBJECTS
+_K_COUNT, _K_POSE, _K_BATCH = _t.PROC_K_COUNT, _t.PROC_K_POSE, _t.PROC_K_BATCH
 _M64 = (1 << 64) - 1
-_CENTRE = (0.7, 0.5, 0.4)
+_CENTRE = _t.PROC_CENTRE
+_ids = _t.proc_ids
 
 
-def _ids(x, device) -> torch.Tensor:
-    return torch.as_tensor(x, dtype=torch.int64, device=device).reshape(-1)
+def _fused(device) -> bool:
+    """One fused HIP launch (ops.procedural_render / procedural_batch) instead
+    of the torch composition in front of ops.scene_render: on a HIP device,
+    unless ``D3D_PROC_FUSED=0`` (A/B runs)."""
+    return torch.device(device).type == "cuda" and os.environ.get("D3D_PROC_FUSED", "1") != "0"
 
 
-def srn_intrinsics(device="cpu") -> torch.Tensor:
-    """The SRN 128 x 128 pinhole K [3,3] (float64)."""
-    return torch.tensor([[SRN_FOCAL_128, 0.0, 64.0], [0.0, SRN_FOCAL_128, 64.0], [0.0, 0.0, 1.0]],
-                        dtype=torch.float64, device=device)
-
-
-def procedural_scene(seed: int, object_ids, device="cpu") -> torch.Tensor:
-    """Scene tables [N,6,16] (float64) of the objects: per slot the 3 x 3 map
-    ``A = diag(1 / axes) R^T`` (world to the unit primitive, row-major), the
-    centre, the albedo and the kind (0 empty, 1 ellipsoid, 2 box)."""
-    dt = torch.float64
-    o = _ids(object_ids, device)
-    N = o.numel()
-    count = 3 + hash_u32(seed ^ _K_COUNT, o) % 4                                  # [N]
-    p = torch.arange(P_MAX, device=o.device)
-    k = torch.arange(14, device=o.device)
-    u = u01(seed, ((o[:, None, None] * P_MAX + p[None, :, None]) * 64 + k[None, None, :])).to(dt)   # [N,6,14]
-    centre = (u[..., 0:3] - 0.5) * torch.tensor(_CENTRE, dtype=dt, device=o.device)
-    axes = 0.08 + 0.22 * u[..., 3:6]
-    q = 2.0 * u[..., 6:10] - 1.0 + 1e-3
-    q = q / torch.sqrt((q * q).sum(-1, keepdim=True))
-    w, x, y, z = q.unbind(-1)
-    R = torch.stack([1 - 2 * (y * y + z * z), 2 * (x * y - w * z), 2 * (x * z + w * y),
-                     2 * (x * y + w * z), 1 - 2 * (x * x + z * z), 2 * (y * z - w * x),
-                     2 * (x * z - w * y), 2 * (y * z + w * x), 1 - 2 * (x * x + y * y)], -1).reshape(N, P_MAX, 3, 3)
-    A = R.transpose(-1, -2) / axes[..., :, None]                                  # diag(1 / axes) R^T
-    albedo = 0.1 + 0.8 * u[..., 10:13]
-    kind = torch.where(u[..., 13] < 0.5, 1.0, 2.0).to(dt)
-    table = torch.cat([A.reshape(N, P_MAX, 9), centre, albedo, kind[..., None]], -1)
-    live = p[None, :] < count[:, None]
-    return torch.where(live[..., None], table, torch.zeros_like(table))
-
-
-def procedural_pose(seed: int, object_ids, view_ids, device="cpu") -> Tuple[torch.Tensor, torch.Tensor]:
-    """Cam-to-world poses of views ``view_ids`` [n] of objects ``object_ids``
-    [n]: R [n,3,3], t [n,3] (float64; OpenCV axes, z up, looking at the origin)."""
-    o, v = _ids(object_ids, device), _ids(view_ids, device)
-    if o.shape != v.shape:
-        raise ValueError(f"procedural_pose: {o.numel()} object ids and {v.numel()} view ids")
-    c = 2 * (o * MAX_VIEWS + v)
-    az = 2.0 * math.pi * u01(seed ^ _K_POSE, c).to(torch.float64)
-    el = 0.05 + 0.95 * u01(seed ^ _K_POSE, c + 1).to(torch.float64)
-    return orbit_look_at(az, el, SRN_RADIUS)
-
-
-def render_views(seed: int, object_ids, view_ids, imgsize: int, device="cpu", aa: int = 3, return_aux: bool = False):
+def render_views(seed: int, object_ids, view_ids, imgsize: int, device="cpu", aa: int = 3, return_aux: bool = False,
+                 return_table: bool = False):
     """``(img [n,3,S,S] fp32, R [n,3,3], t [n,3], K [n,3,3])`` of the listed
     (object, view) pairs (``return_aux``: ``img`` is ``ops.scene_render``'s
-    (img, depth, prim))."""
+    (img, depth, prim); ``return_table``: also the scene tables [n,6,16])."""
     o = _ids(object_ids, device)
-    table = procedural_scene(seed, o, device)
-    R, t = procedural_pose(seed, o, view_ids, device)
     K = srn_intrinsics(o.device).expand(o.numel(), 3, 3).contiguous()
-    return ops.scene_render(table, R, t, K, imgsize, imgsize, aa=aa, return_aux=return_aux), R, t, K
+    if _fused(o.device) and o.numel():
+        out = ops.procedural_render(seed, o, _ids(view_ids, device), imgsize, imgsize, aa=aa, return_aux=return_aux)
+        img, R, t, table = out[:4]
+        img = (img, out[4], out[5]) if return_aux else img
+    else:
+        table = procedural_scene(seed, o, device)
+        R, t = procedural_pose(seed, o, view_ids, device)
+        img = ops.scene_render(table, R, t, K, imgsize, imgsize, aa=aa, return_aux=return_aux)
+    return (img, R, t, K, table) if return_table else (img, R, t, K)
 
 
 def split_size(objects: int, split: str) -> int:
@@ -119,12 +93,6 @@ def split_size(objects: int, split: str) -> int:
         raise ValueError(f"objects must be in [0, 2^31], got {objects}")
     n = objects or MAX_OBJECTS
     return n // 10 if split == "val" else n - n // 10
-
-
-def split_object(rank, split: str):
-    """The id of the split's ``rank``-th object (int or int64 tensor): ids with
-    ``o % 10 == 9`` are the held-out split, the rest the training split."""
-    return 10 * rank + 9 if split == "val" else rank + rank // 9
 
 
 class ProceduralBatches:
@@ -158,20 +126,21 @@ class ProceduralBatches:
 
     def draw(self, i: int):
         """(object ids [B], view ids [B,2]) of batch ``i`` (int64, on the device)."""
-        s = ((self.seed * 0x2545F4914F6CDD1D + _K_BATCH) + (i + 1) * GOLDEN) & _M64
-        g = torch.arange(self.B, dtype=torch.int64, device=self.device) + self.example_offset
-        obj = split_object(hash_u32(s, 4 * g) % self.n_objects, self.split)
-        v0 = hash_u32(s, 4 * g + 1) % self.views
-        v1 = (v0 + 1 + hash_u32(s, 4 * g + 2) % (self.views - 1)) % self.views
-        return obj, torch.stack([v0, v1], 1)
+        return _t.procedural_draw(self.seed, i, self.B, n_objects=self.n_objects, views=self.views, split=self.split,
+                                  example_offset=self.example_offset, device=self.device)
 
     def __next__(self):
         B, S = self.B, self.S
-        obj, view = self.draw(self.i)
-        self.i += 1
+        i, self.i = self.i, self.i + 1
+        K = self.K.expand(B, 3, 3).contiguous()
+        if _fused(self.device) and B > 0:           # draw, tables, poses and render: one launch
+            _, _, img, R, t = ops.procedural_batch(self.seed, i, B, S, S, n_objects=self.n_objects, views=self.views,
+                                                   split=self.split, example_offset=self.example_offset, aa=self.aa,
+                                                   device=self.device)
+            return img, R, t, K
+        obj, view = self.draw(i)
         table = procedural_scene(self.seed, obj, self.device)
         R, t = procedural_pose(self.seed, obj.repeat_interleave(2), view.reshape(-1), self.device)
-        K = self.K.expand(B, 3, 3).contiguous()
         img = ops.scene_render(table.repeat_interleave(2, 0), R, t, K.repeat_interleave(2, 0), S, S, aa=self.aa)
         return img.reshape(B, 2, 3, S, S), R.reshape(B, 2, 3, 3), t.reshape(B, 2, 3), K
 
@@ -195,10 +164,11 @@ def procedural_objects(seed: int, instances: int, views: Sequence[int], imgsize:
         device = "cuda" if torch.cuda.is_available() else "cpu"
     ids = [split_object(r, split) for r in range(instances)]
     nv = len(views)
-    img, R, t, _ = render_views(seed, [o for o in ids for _ in views], views * len(ids), imgsize, device, aa)
+    img, R, t, _, table = render_views(seed, [o for o in ids for _ in views], views * len(ids), imgsize, device, aa,
+                                       return_table=True)
     img, R, t = img.cpu(), R.float().cpu(), t.float().cpu()
     K = srn_intrinsics().float()
-    scene = procedural_scene(seed, ids)                 # the geometry, for the geometry-aware scores
+    scene = table[::nv].cpu()                           # the geometry, for the geometry-aware scores
     return [EvalObject(f"proc-{seed}-{o}", {v: img[j * nv + i] for i, v in enumerate(views)},
                        {v: R[j * nv + i] for i, v in enumerate(views)},
                        {v: t[j * nv + i] for i, v in enumerate(views)}, K.clone(), scene=scene[j].clone())

@@ -250,6 +250,44 @@ def scene_render(table, R, t, K, H: int, W: int, *, aa: int = 3, return_aux: boo
     return _t.scene_render(table, R, t, K, H, W, aa=aa, return_aux=return_aux)
 
 
+def procedural_render(seed: int, object_ids, view_ids, H: int, W: int, *, aa: int = 3, return_aux: bool = False):
+    """Procedural scenes from their ids in one launch: ``(img [n,3,H,W] fp32 in
+    [-1, 1], R [n,3,3], t [n,3], table [n,6,16])`` (the poses and the scene
+    tables fp64) of view ``view_ids[i]`` of object ``object_ids[i]`` under
+    ``seed`` -- what ``data.procedural_scene``, ``data.procedural_pose`` and
+    :func:`scene_render` give together.  The ids are 1-D int64 tensors of one
+    length on the target device, objects in ``[0, 2^31)``, views in ``[0,
+    4096)`` (checked, which reads them back once); ``aa`` in 1..4.
+    ``return_aux``: also ``depth`` [n,H,W] fp32 and ``prim`` [n,H,W] int32 of
+    the pixel-centre ray.  HIP (``csrc/procedural.hip``: the tables and poses
+    are built in the render kernel's block prologue) on the GPU, the float64
+    torch composition on the CPU."""
+    n = _t.procedural_render_check(seed, object_ids, view_ids, H, W, aa)
+    if object_ids.is_cuda and n > 0 and use_hip(object_ids, any_dtype=True):
+        return _h().procedural_render(seed, object_ids, view_ids, H, W, aa=aa, return_aux=return_aux)
+    return _t.procedural_render(seed, object_ids, view_ids, H, W, aa=aa, return_aux=return_aux)
+
+
+def procedural_batch(seed: int, batch_index: int, B: int, H: int, W: int, *, n_objects: int, views: int, split: str,
+                     example_offset: int = 0, aa: int = 3, device=None):
+    """A procedural training batch in one launch: ``(obj [B] int64, view [B,2]
+    int64, img [B,2,3,H,W] fp32, R [B,2,3,3] fp64, t [B,2,3] fp64)``.  Example
+    ``g = example_offset + j`` of batch ``batch_index`` draws one of the
+    ``n_objects`` objects of ``split`` ("train" / "val") and two distinct views
+    of ``views`` (2..4096) from the counter hash keyed by ``(seed, batch_index,
+    g)`` (``data.ProceduralBatches.draw``), so a shard reproduces its rows of
+    the full batch; the two frames are rendered as :func:`procedural_render`
+    renders them.  ``device``: where the batch is made (default: the GPU when
+    there is one).  No host synchronise.  HIP (``csrc/procedural.hip``) on the
+    GPU, the float64 torch composition on the CPU."""
+    _t.procedural_batch_check(seed, batch_index, B, H, W, n_objects, views, split, example_offset, aa)
+    device = torch.device(device if device is not None else ("cuda" if torch.cuda.is_available() else "cpu"))
+    kw = dict(n_objects=n_objects, views=views, split=split, example_offset=example_offset, aa=aa, device=device)
+    if device.type == "cuda" and B > 0 and use_hip(torch.empty(0, device=device), any_dtype=True):
+        return _h().procedural_batch(seed, batch_index, B, H, W, **kw)
+    return _t.procedural_batch(seed, batch_index, B, H, W, **kw)
+
+
 def view_consistency(table, K, R_src, t_src, img_src, R_tgt, t_tgt, img_tgt, ref=None, *,
                      return_class: bool = False):
     """Geometry-aware scores of N (source view, target view) pairs of
@@ -452,7 +490,7 @@ posenc_nerf = _t.posenc_nerf
 
 __all__ = ["diffusion_inputs", "diff_loss_nhwc", "diff_loss_rows", "loss_bins_add", "group_norm", "gn_film", "conv3x3", "linear", "film_batch", "cat_gn_silu_dense", "cond_conv", "ray_posenc_dir",
            "ray_origin_pe", "ray_conditioning", "attention", "avgpool2", "upsample2",
-           "silu", "logsnr_mlp", "ray_posenc", "image_metrics", "scene_render", "view_consistency", "ensemble_stats", "field_render", "field_loss_grad", "field_batch_loss_grad", "field_adam_tv", "field_geometry", "depth_consistency", "psnr", "posenc_ddpm", "camera_rays", "posenc_nerf", "set_backend",
+           "silu", "logsnr_mlp", "ray_posenc", "image_metrics", "scene_render", "procedural_render", "procedural_batch", "view_consistency", "ensemble_stats", "field_render", "field_loss_grad", "field_batch_loss_grad", "field_adam_tv", "field_geometry", "depth_consistency", "psnr", "posenc_ddpm", "camera_rays", "posenc_nerf", "set_backend",
            "use_hip", "load_library", "library_error", "lib_path"]
 
 

@@ -129,6 +129,10 @@ SIGNATURES = {
     "d3d_image_metrics": [P, P, I, I, I, I, I, C.POINTER(C.c_double), P, P, P],
     # scene.hip
     "d3d_scene_render": [P, P, P, P, I, I, I, I, I, P, P, P, P],
+    # procedural.hip (K: 9 host doubles)
+    "d3d_procedural_render": [U64, P, P, L, I, I, I, I, C.c_double, C.POINTER(C.c_double), P, P, P, P, P, P, P],
+    "d3d_procedural_batch": [U64, U64, L, I, I, L, L, I, I, I, I, C.c_double, C.POINTER(C.c_double), P, P, P, P, P,
+                             P, P],
     # consistency.hip
     "d3d_view_consistency": [P, P, P, P, P, P, P, P, P, I, I, I, I, P, P, P, P],
     # ensemble.hip

@@ -2943,6 +2943,52 @@ def scene_render(table, R, t, K, H, W, *, aa=3, return_aux=False):
     return (img, depth, prim) if return_aux else img
 
 
+_SRN_K = (ctypes.c_double * 9)(*_t.SRN_K)
+_M64 = (1 << 64) - 1
+
+
+def procedural_render(seed, object_ids, view_ids, H, W, *, aa=3, return_aux=False):
+    """(img [n,3,H,W] fp32, R [n,3,3], t [n,3], table [n,6,16] fp64; with
+    ``return_aux`` also depth and prim) of the int64 (object, view) id pairs
+    (csrc/procedural.hip: scene_render's thread-per-pixel kernel with the
+    tables and poses built in its block prologue, one launch; the numbers of
+    ``torch_impl.procedural_render``).  Graph-capturable."""
+    n = object_ids.numel()
+    o, v = object_ids.contiguous(), view_ids.contiguous()
+    dev = o.device
+    img = torch.empty(n, 3, H, W, dtype=F32, device=dev)
+    R = torch.empty(n, 3, 3, dtype=torch.float64, device=dev)
+    t = torch.empty(n, 3, dtype=torch.float64, device=dev)
+    table = torch.empty(n, _t.SCENE_SLOTS, _t.SCENE_WORDS, dtype=torch.float64, device=dev)
+    depth = torch.empty(n, H, W, dtype=F32, device=dev) if return_aux else None
+    prim = torch.empty(n, H, W, dtype=torch.int32, device=dev) if return_aux else None
+    if n > 0:
+        _chk(_lib.d3d_procedural_render(int(seed) & _M64, o.data_ptr(), v.data_ptr(), n, H, W, aa, _t.SCENE_REF,
+                                        _t.SRN_RADIUS, _SRN_K, img.data_ptr(), R.data_ptr(), t.data_ptr(),
+                                        table.data_ptr(), _ptr(depth), _ptr(prim), _st()), "procedural_render")
+    return (img, R, t, table, depth, prim) if return_aux else (img, R, t, table)
+
+
+def procedural_batch(seed, batch_index, B, H, W, *, n_objects, views, split, example_offset=0, aa=3, device="cuda"):
+    """(obj [B], view [B,2] int64, img [B,2,3,H,W] fp32, R [B,2,3,3], t [B,2,3]
+    fp64) of a training batch (csrc/procedural.hip in DRAW mode: the kernel
+    also draws the ids from the batch key; one launch, no host synchronise;
+    the numbers of ``torch_impl.procedural_batch``).  Graph-capturable."""
+    dev = torch.device(device)
+    with torch.cuda.device(dev):
+        obj = torch.empty(B, dtype=torch.int64, device=dev)
+        view = torch.empty(B, 2, dtype=torch.int64, device=dev)
+        img = torch.empty(B, 2, 3, H, W, dtype=F32, device=dev)
+        R = torch.empty(B, 2, 3, 3, dtype=torch.float64, device=dev)
+        t = torch.empty(B, 2, 3, dtype=torch.float64, device=dev)
+        if B > 0:
+            _chk(_lib.d3d_procedural_batch(int(seed) & _M64, _t.procedural_batch_key(seed, batch_index), n_objects,
+                                           views, int(split == "val"), example_offset, B, H, W, aa, _t.SCENE_REF,
+                                           _t.SRN_RADIUS, _SRN_K, obj.data_ptr(), view.data_ptr(), img.data_ptr(),
+                                           R.data_ptr(), t.data_ptr(), None, _st()), "procedural_batch")
+    return obj, view, img, R, t
+
+
 def view_consistency(table, K, R_src, t_src, img_src, R_tgt, t_tgt, img_tgt, ref=None, *, return_class=False):
     """stats [N,8] fp64 (and, with ``return_class``, the class plane [N,H,W]
     int32) of N (source, target) pairs over their fp64 scene tables and

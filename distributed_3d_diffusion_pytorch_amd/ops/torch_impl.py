@@ -639,6 +639,179 @@ def scene_render(table: torch.Tensor, R: torch.Tensor, t: torch.Tensor, K: torch
     return img, depth.float(), prim.to(torch.int32)
 
 
+# The rule that turns (seed, object id, view id) into a scene table and a pose
+# (data/procedural.py states it; csrc/procedural.hip is its fused HIP form).
+# These float64 functions are the CPU path of ops.procedural_render /
+# ops.procedural_batch and the kernel's oracle.
+PROC_MAX_VIEWS = 4096                # views of one object (the pose counter's stride)
+PROC_MAX_OBJECTS = 1 << 31
+PROC_K_COUNT = 0x5BD1E995
+PROC_K_POSE = 0x7F4A7C15
+PROC_K_BATCH = 0x70726F6365647572    # "procedur": keeps the batch draw apart from the scene and pose draws
+PROC_CENTRE = (0.7, 0.5, 0.4)
+SRN_FOCAL_128 = 131.25               # SRN cars 128^2 pinhole (fx = fy), principal point at 64
+SRN_RADIUS = 1.3
+SRN_K = (SRN_FOCAL_128, 0.0, 64.0, 0.0, SRN_FOCAL_128, 64.0, 0.0, 0.0, 1.0)
+
+
+def srn_intrinsics(device="cpu") -> torch.Tensor:
+    """The SRN 128 x 128 pinhole K [3,3] (float64)."""
+    return torch.tensor(SRN_K, dtype=torch.float64, device=device).reshape(3, 3)
+
+
+def orbit_look_at(az: torch.Tensor, el: torch.Tensor, radius: float = SRN_RADIUS):
+    """The look-at pose (OpenCV cam-to-world, z up) on the orbit at azimuth
+    ``az`` and elevation ``el`` (float64 [n]): R [n,3,3], t [n,3]."""
+    pos = radius * torch.stack([torch.cos(el) * torch.cos(az), torch.cos(el) * torch.sin(az), torch.sin(el)], -1)
+    fwd = -pos / pos.norm(dim=-1, keepdim=True)
+    up = torch.tensor([0.0, 0.0, 1.0], dtype=torch.float64, device=pos.device).expand_as(fwd)
+    right = torch.linalg.cross(fwd, up)
+    right = right / right.norm(dim=-1, keepdim=True)
+    down = torch.linalg.cross(fwd, right)
+    R = torch.stack([right, down, fwd], dim=-1)
+    return R, pos
+
+
+def proc_ids(x, device) -> torch.Tensor:
+    return torch.as_tensor(x, dtype=torch.int64, device=device).reshape(-1)
+
+
+def procedural_scene(seed: int, object_ids, device="cpu") -> torch.Tensor:
+    """Scene tables [N,6,16] (float64) of the objects: per slot the 3 x 3 map
+    ``A = diag(1 / axes) R^T`` (world to the unit primitive, row-major), the
+    centre, the albedo and the kind (0 empty, 1 ellipsoid, 2 box)."""
+    dt = torch.float64
+    o = proc_ids(object_ids, device)
+    N = o.numel()
+    count = 3 + hash_u32(seed ^ PROC_K_COUNT, o) % 4                              # [N]
+    p = torch.arange(SCENE_SLOTS, device=o.device)
+    k = torch.arange(14, device=o.device)
+    u = u01(seed, ((o[:, None, None] * SCENE_SLOTS + p[None, :, None]) * 64 + k[None, None, :])).to(dt)   # [N,6,14]
+    centre = (u[..., 0:3] - 0.5) * torch.tensor(PROC_CENTRE, dtype=dt, device=o.device)
+    axes = 0.08 + 0.22 * u[..., 3:6]
+    q = 2.0 * u[..., 6:10] - 1.0 + 1e-3
+    q = q / torch.sqrt((q * q).sum(-1, keepdim=True))
+    w, x, y, z = q.unbind(-1)
+    R = torch.stack([1 - 2 * (y * y + z * z), 2 * (x * y - w * z), 2 * (x * z + w * y),
+                     2 * (x * y + w * z), 1 - 2 * (x * x + z * z), 2 * (y * z - w * x),
+                     2 * (x * z - w * y), 2 * (y * z + w * x), 1 - 2 * (x * x + y * y)], -1).reshape(N, SCENE_SLOTS, 3, 3)
+    A = R.transpose(-1, -2) / axes[..., :, None]                                  # diag(1 / axes) R^T
+    albedo = 0.1 + 0.8 * u[..., 10:13]
+    kind = torch.where(u[..., 13] < 0.5, 1.0, 2.0).to(dt)
+    table = torch.cat([A.reshape(N, SCENE_SLOTS, 9), centre, albedo, kind[..., None]], -1)
+    live = p[None, :] < count[:, None]
+    return torch.where(live[..., None], table, torch.zeros_like(table))
+
+
+def procedural_pose(seed: int, object_ids, view_ids, device="cpu"):
+    """Cam-to-world poses of views ``view_ids`` [n] of objects ``object_ids``
+    [n]: R [n,3,3], t [n,3] (float64; OpenCV axes, z up, looking at the origin)."""
+    o, v = proc_ids(object_ids, device), proc_ids(view_ids, device)
+    if o.shape != v.shape:
+        raise ValueError(f"procedural_pose: {o.numel()} object ids and {v.numel()} view ids")
+    c = 2 * (o * PROC_MAX_VIEWS + v)
+    az = 2.0 * math.pi * u01(seed ^ PROC_K_POSE, c).to(torch.float64)
+    el = 0.05 + 0.95 * u01(seed ^ PROC_K_POSE, c + 1).to(torch.float64)
+    return orbit_look_at(az, el, SRN_RADIUS)
+
+
+def split_object(rank, split: str):
+    """The id of the split's ``rank``-th object (int or int64 tensor): ids with
+    ``o % 10 == 9`` are the held-out split, the rest the training split."""
+    return 10 * rank + 9 if split == "val" else rank + rank // 9
+
+
+def procedural_batch_key(seed: int, batch_index: int) -> int:
+    """(seed, batch index) folded into the 64-bit key of the batch draw."""
+    return ((seed * 0x2545F4914F6CDD1D + PROC_K_BATCH) + (batch_index + 1) * GOLDEN) & _M64
+
+
+def procedural_draw(seed: int, batch_index: int, B: int, *, n_objects: int, views: int, split: str,
+                    example_offset: int = 0, device="cpu"):
+    """(object ids [B], view ids [B,2]) of the batch (int64): example ``g =
+    example_offset + j`` draws the ``hash_u32(s, 4 g) % n_objects``-th object
+    of the split and two distinct views of ``views``."""
+    s = procedural_batch_key(seed, batch_index)
+    g = torch.arange(B, dtype=torch.int64, device=device) + example_offset
+    obj = split_object(hash_u32(s, 4 * g) % n_objects, split)
+    v0 = hash_u32(s, 4 * g + 1) % views
+    v1 = (v0 + 1 + hash_u32(s, 4 * g + 2) % (views - 1)) % views
+    return obj, torch.stack([v0, v1], 1)
+
+
+def _proc_int(name, op, v, lo, hi=None):
+    if isinstance(v, bool) or not isinstance(v, int):
+        raise ValueError(f"{op}: {name} must be an int, got {v!r}")
+    if v < lo or (hi is not None and v > hi):
+        raise ValueError(f"{op}: {name} must be in {lo}..{'' if hi is None else hi}, got {v}")
+
+
+def procedural_render_check(seed, object_ids, view_ids, H, W, aa) -> int:
+    """Argument check shared by both backends (ValueError); returns n.  The
+    range check of the ids reads them back (one host synchronise on the GPU)."""
+    op = "procedural_render"
+    _proc_int("seed", op, seed, -(1 << 63), _M64)
+    for name, x in (("object_ids", object_ids), ("view_ids", view_ids)):
+        if not isinstance(x, torch.Tensor) or x.dtype != torch.int64 or x.dim() != 1:
+            raise ValueError(f"{op}: {name} must be a 1-D int64 tensor")
+    if object_ids.shape != view_ids.shape or object_ids.device != view_ids.device:
+        raise ValueError(f"{op}: {object_ids.numel()} object ids on {object_ids.device} and {view_ids.numel()} view "
+                         f"ids on {view_ids.device}")
+    _proc_int("H", op, H, 1)
+    _proc_int("W", op, W, 1)
+    _proc_int("aa", op, aa, 1, 4)
+    if object_ids.numel():
+        lo, hi, vlo, vhi = torch.stack([object_ids.min(), object_ids.max(), view_ids.min(), view_ids.max()]).tolist()
+        if lo < 0 or hi >= PROC_MAX_OBJECTS:
+            raise ValueError(f"{op}: object ids must be in [0, 2^31), got {lo}..{hi}")
+        if vlo < 0 or vhi >= PROC_MAX_VIEWS:
+            raise ValueError(f"{op}: view ids must be in [0, {PROC_MAX_VIEWS}), got {vlo}..{vhi}")
+    return object_ids.numel()
+
+
+def procedural_batch_check(seed, batch_index, B, H, W, n_objects, views, split, example_offset, aa) -> None:
+    """Argument check shared by both backends (ValueError)."""
+    op = "procedural_batch"
+    _proc_int("seed", op, seed, -(1 << 63), _M64)
+    _proc_int("batch_index", op, batch_index, 0, 1 << 62)
+    _proc_int("B", op, B, 0, 1 << 30)
+    _proc_int("H", op, H, 1)
+    _proc_int("W", op, W, 1)
+    _proc_int("aa", op, aa, 1, 4)
+    _proc_int("views", op, views, 2, PROC_MAX_VIEWS)
+    _proc_int("n_objects", op, n_objects, 1, PROC_MAX_OBJECTS)
+    _proc_int("example_offset", op, example_offset, 0, 1 << 60)
+    if split not in ("train", "val"):
+        raise ValueError(f"{op}: split {split!r}: expected 'train' or 'val'")
+    if split_object(n_objects - 1, split) >= PROC_MAX_OBJECTS:
+        raise ValueError(f"{op}: {n_objects} {split} objects reach past id 2^31")
+
+
+def procedural_render(seed: int, object_ids, view_ids, H: int, W: int, *, aa: int = 3, return_aux: bool = False):
+    """``(img [n,3,H,W] f32, R [n,3,3], t [n,3], table [n,6,16])`` (and, with
+    ``return_aux``, depth and prim) of the listed (object, view) pairs: the
+    composition of ``procedural_scene``, ``procedural_pose`` and ``scene_render``."""
+    n = procedural_render_check(seed, object_ids, view_ids, H, W, aa)
+    dev = object_ids.device
+    table = procedural_scene(seed, object_ids, dev)
+    R, t = procedural_pose(seed, object_ids, view_ids, dev)
+    K = srn_intrinsics(dev).expand(n, 3, 3).contiguous()
+    out = scene_render(table, R, t, K, H, W, aa=aa, return_aux=return_aux)
+    return (out[0], R, t, table, out[1], out[2]) if return_aux else (out, R, t, table)
+
+
+def procedural_batch(seed: int, batch_index: int, B: int, H: int, W: int, *, n_objects: int, views: int, split: str,
+                     example_offset: int = 0, aa: int = 3, device="cpu"):
+    """``(obj [B] i64, view [B,2] i64, img [B,2,3,H,W] f32, R [B,2,3,3], t
+    [B,2,3])`` of a training batch: ``procedural_draw``, then the render of the
+    2 B (object, view) pairs."""
+    procedural_batch_check(seed, batch_index, B, H, W, n_objects, views, split, example_offset, aa)
+    obj, view = procedural_draw(seed, batch_index, B, n_objects=n_objects, views=views, split=split,
+                                example_offset=example_offset, device=device)
+    img, R, t, _ = procedural_render(seed, obj.repeat_interleave(2), view.reshape(-1), H, W, aa=aa)
+    return obj, view, img.reshape(B, 2, 3, H, W), R.reshape(B, 2, 3, 3), t.reshape(B, 2, 3)
+
+
 # ------------------------------------------------ geometry-aware evaluation ---
 # Co-visible PSNR and reprojection consistency on the procedural scenes
 # (csrc/consistency.hip holds the rule in full).
