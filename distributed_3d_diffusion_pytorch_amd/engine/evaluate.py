@@ -158,7 +158,8 @@ def evaluate_objects(model, objects: Sequence[EvalObject], input_view: int = 0, 
                      autoregressive: bool = False, seed: int = 0, device=None, ref_quirk: bool = False,
                      graph: Optional[bool] = None, keep_images: bool = False,
                      on_view: Optional[Callable] = None, solver: str = "ancestral", eta: float = 0.0,
-                     spacing: str = "t", prediction: str = "eps", consistency: bool = False, samples: int = 1):
+                     spacing: str = "t", prediction: str = "eps", consistency: bool = False, samples: int = 1,
+                     swd: Optional[dict] = None):
     """Generate ``views`` of every object from its ``input_view`` and score
     them.  Returns ``(rows, images)``: one row ``{instance, view, w, chain,
     mse, psnr, ssim}`` per (object, view, w) -- ``chain`` the global chain
@@ -203,7 +204,14 @@ def evaluate_objects(model, objects: Sequence[EvalObject], input_view: int = 0, 
     all C) and the row gains ``n_<class>``, ``bias_<class>``,
     ``spread_<class>`` and ``mse_samples_<class>`` for background, disoccluded
     and covisible (None where the count is 0).  ``samples = 1`` is the path
-    above, chain numbering and return value included."""
+    above, chain numbering and return value included.
+
+    ``swd`` (a dict with any of ``patches``, ``dirs``, ``seed``, ``levels``):
+    the generated images (sample 0 of every view when ``samples`` > 1) and
+    their ground truth stay on the device, and after the loop every guidance
+    weight's set is scored against the ground-truth set by one
+    ``ops.sliced_wasserstein`` call (:func:`swd_block`); the block is then the
+    last element of the return value."""
     dev = torch.device(device) if device is not None else next(model.parameters()).device
     nw, C = len(w), int(samples)
     if C < 1:
@@ -215,6 +223,8 @@ def evaluate_objects(model, objects: Sequence[EvalObject], input_view: int = 0, 
     images: Dict[tuple, torch.Tensor] = {}
     if consistency:
         _scenes(objects)
+    swd_gen: List[List[torch.Tensor]] = [[] for _ in range(nw)]
+    swd_real: List[torch.Tensor] = []
     for s in range(0, len(objects), max(int(batch), 1)):
         objs = objects[s:s + max(int(batch), 1)]
         G = len(objs)
@@ -239,6 +249,10 @@ def evaluate_objects(model, objects: Sequence[EvalObject], input_view: int = 0, 
             gt = torch.stack([o.imgs[v] for o in objs]).to(dev)
             mse, ssim = ops.image_metrics(out, gt.repeat_interleave(nc, 0), quantize=True)
             mse_l, ssim_l = mse.double().cpu().tolist(), ssim.double().cpu().tolist()
+            if swd is not None:
+                for i in range(nw):
+                    swd_gen[i].append(out.reshape(G, nw, C, *out.shape[1:])[:, i, 0])
+                swd_real.append(gt.float())
             klass = None
             if consistency:
                 kept[int(v)] = out.contiguous()
@@ -293,7 +307,41 @@ def evaluate_objects(model, objects: Sequence[EvalObject], input_view: int = 0, 
                                 if C > 1:
                                     pair_rows[-1]["sample"] = c
     res = (rows, images, pair_rows) if consistency else (rows, images)
-    return res + (ensemble_rows,) if C > 1 else res
+    res = res + (ensemble_rows,) if C > 1 else res
+    if swd is not None:
+        res = res + (swd_block([torch.cat(g) for g in swd_gen], torch.cat(swd_real), w, **swd),)
+    return res
+
+
+def swd_block(generated: Sequence[torch.Tensor], real: torch.Tensor, w: Sequence[float], patches: int = 128,
+              dirs: int = 512, seed: int = 0, levels: Optional[int] = None) -> dict:
+    """The sliced Wasserstein distance of each guidance weight's generated set
+    ``generated[i]`` [n,3,H,W] against the ground-truth set ``real`` [n,3,H,W]:
+    ``{levels, patches, dirs, seed, n_images, per_w: {"<w>": {levels: [...],
+    mean}}}``.  ``patches`` is the effective count per image and level,
+    ``min(patches, 16384 // n)`` (the op's limit; 0 is a ValueError); one
+    direction set serves every call.  With an even n, ``split_floor`` is the
+    same score between the even- and the odd-indexed ground-truth images, at
+    the same patches per image and the same directions: the metric's sampling
+    noise at half this set size, the scale the per-w scores are read against."""
+    from ..ops import torch_impl as _t
+    n, _, H, W = real.shape
+    P = min(int(patches), _t.SWD_MAX_N // n)
+    if P < 1:
+        raise ValueError(f"swd: {n} images leave no patch per image under the limit of {_t.SWD_MAX_N} descriptors")
+    L = _t.swd_default_levels(H, W) if levels is None else int(levels)
+    theta = _t.swd_directions(seed, L, dirs, real.device)
+    real = real.float().contiguous()
+
+    def score(a, b):
+        v = ops.sliced_wasserstein(a.float().contiguous(), b, levels=L, patches=P, dirs=theta, seed=seed).tolist()
+        return {"levels": v, "mean": math.fsum(v) / len(v)}
+
+    out = {"levels": L, "patches": P, "dirs": int(dirs), "seed": int(seed), "n_images": int(n),
+           "per_w": {f"{float(wv):g}": score(g, real) for wv, g in zip(w, generated)}}
+    if n % 2 == 0:
+        out["split_floor"] = score(real[0::2], real[1::2].contiguous())
+    return out
 
 
 def _spread_skill(V: float, B: float, C: int):

@@ -479,6 +479,37 @@ def depth_consistency(depth, images, K, R, t, *, tol: float, rescale_from: int =
                                   return_class=return_class)
 
 
+def sliced_wasserstein(a, b, *, levels=None, patches: int = 128, dirs=512, seed: int = 0, quantize: bool = True):
+    """The sliced Wasserstein distance (Karras et al. 2018) between two image
+    sets ``a`` (generated) and ``b`` (real), fp32 ``[N,3,H,W]`` in [-1, 1],
+    contiguous, of one shape: a distance between the sets' distributions, not
+    between paired images, that needs no trained network.  Both sets are
+    mapped to [0, 1] (``quantize`` as in ``image_metrics``) and decomposed into
+    ``levels`` Laplacian-pyramid levels (``None``: the most whose coarsest side
+    is at least 16); every image gives ``patches`` 7 x 7 x 3 patches per level
+    at corners drawn from ``seed`` (the same for both sets), normalised per
+    set, level and channel; the patches are projected onto ``dirs`` unit
+    directions (an int: ``torch_impl.swd_directions(seed, levels, dirs)``; or a
+    ready fp64 ``[levels,D,147]`` tensor) and the sorted projections of the two
+    sets compared.  Returns ``swd`` fp64 ``[levels]``, fine to coarse, raw (the
+    paper prints it x 1000); exactly 0 for identical sets; bitwise
+    reproducible.  H, W at most 128 and divisible by ``2^(levels - 1)``, the
+    coarsest level at least 7 x 7, ``N * patches`` at most 16384, else
+    ValueError.  HIP (``csrc/swd.hip``, which states the rule) on the GPU, the
+    float64 torch form on the CPU."""
+    if not isinstance(a, torch.Tensor) or a.dim() != 4:
+        raise ValueError(f"sliced_wasserstein: a must be a [N,3,H,W] tensor, got {type(a).__name__}")
+    if levels is None:
+        levels = _t.swd_default_levels(int(a.shape[2]), int(a.shape[3]))
+    if isinstance(dirs, int) and not isinstance(dirs, bool):
+        if isinstance(levels, bool) or not isinstance(levels, int) or levels < 1 or dirs < 1:
+            raise ValueError(f"sliced_wasserstein: levels and dirs must be at least 1, got {levels!r} and {dirs!r}")
+        dirs = _t.swd_directions(seed, levels, dirs, a.device)
+    _t.sliced_wasserstein_check(a, b, dirs, levels=levels, patches=patches, seed=seed)
+    impl = _h() if a.is_cuda and use_hip(a, any_dtype=True) else _t
+    return impl.sliced_wasserstein(a, b, dirs=dirs, levels=levels, patches=patches, seed=seed, quantize=quantize)
+
+
 def psnr(mse):
     """``10 log10(1 / mse)`` on the [0, 1] scale; ``+inf`` where ``mse == 0``."""
     return -10.0 * torch.log10(torch.as_tensor(mse, dtype=torch.float32))
@@ -490,7 +521,7 @@ posenc_nerf = _t.posenc_nerf
 
 __all__ = ["diffusion_inputs", "diff_loss_nhwc", "diff_loss_rows", "loss_bins_add", "group_norm", "gn_film", "conv3x3", "linear", "film_batch", "cat_gn_silu_dense", "cond_conv", "ray_posenc_dir",
            "ray_origin_pe", "ray_conditioning", "attention", "avgpool2", "upsample2",
-           "silu", "logsnr_mlp", "ray_posenc", "image_metrics", "scene_render", "procedural_render", "procedural_batch", "view_consistency", "ensemble_stats", "field_render", "field_loss_grad", "field_batch_loss_grad", "field_adam_tv", "field_geometry", "depth_consistency", "psnr", "posenc_ddpm", "camera_rays", "posenc_nerf", "set_backend",
+           "silu", "logsnr_mlp", "ray_posenc", "image_metrics", "scene_render", "procedural_render", "procedural_batch", "view_consistency", "ensemble_stats", "field_render", "field_loss_grad", "field_batch_loss_grad", "field_adam_tv", "field_geometry", "depth_consistency", "sliced_wasserstein", "psnr", "posenc_ddpm", "camera_rays", "posenc_nerf", "set_backend",
            "use_hip", "load_library", "library_error", "lib_path"]
 
 

@@ -152,6 +152,9 @@ SIGNATURES = {
     # depth_consistency.hip
     "d3d_depth_consistency_blocks": [I, I],
     "d3d_depth_consistency": [P, P, P, P, P, I, I, I, I, C.c_double, I, P, P, P, P],
+    # swd.hip
+    "d3d_swd_cfg": [I],
+    "d3d_sliced_wasserstein": [P, P, P, L, I, I, I, I, I, U64, I, P, P, P, P, P],
 }
 
 

@@ -3158,3 +3158,25 @@ def depth_consistency(depth, images, K, R, t, *, tol, rescale_from=128, return_c
                                         F, V, H, W, float(tol), int(rescale_from), part.data_ptr(), stats.data_ptr(),
                                         _ptr(cls), _st()), "depth_consistency")
     return (stats, cls) if return_class else stats
+
+
+# -------------------------------------------- sliced Wasserstein distance ---
+def sliced_wasserstein(a, b, *, dirs, levels, patches, seed, quantize=True):
+    """swd fp64 [L] of two image sets fp32 [N,3,H,W] under ``dirs`` fp64
+    [L,D,147] (csrc/swd.hip: the Laplacian pyramids built per plane in LDS, the
+    patch statistics, then one workgroup per (direction, level) that projects
+    both sets' patches straight from the planes and sorts the keys in
+    registers, across lanes and through LDS; the numbers of
+    ``torch_impl.sliced_wasserstein`` within the keys' fp32 rounding).
+    Graph-capturable."""
+    N, H, W, L, P, D = _t.sliced_wasserstein_check(a, b, dirs, levels=levels, patches=patches, seed=seed)
+    dev = a.device
+    lap = torch.empty(sum(6 * N * (H >> l) * (W >> l) for l in range(L)), dtype=torch.float64, device=dev)
+    stat = torch.empty(2, L, 3, 2, dtype=torch.float64, device=dev)
+    part = torch.empty(L, D, dtype=torch.float64, device=dev)
+    swd = torch.empty(L, dtype=torch.float64, device=dev)
+    _chk(_lib.d3d_sliced_wasserstein(a.data_ptr(), b.data_ptr(), dirs.data_ptr(), N, H, W, L, P, D,
+                                     (int(seed) ^ _t.SWD_K_PATCH) & ((1 << 64) - 1), int(bool(quantize)),
+                                     lap.data_ptr(), stat.data_ptr(), part.data_ptr(), swd.data_ptr(), _st()),
+         "sliced_wasserstein")
+    return swd

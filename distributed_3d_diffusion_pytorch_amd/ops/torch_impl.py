@@ -1549,3 +1549,141 @@ def _depth_consistency(depth, images, K, R, t, *, tol, rescale_from, return_clas
     if cond is not None:
         cond["margin"] = margin[0]
     return (stats, cls) if return_class else stats
+
+
+# -------------------------------------------- sliced Wasserstein distance ---
+# The distance between two image sets on Laplacian-pyramid patches (Karras et
+# al. 2018), one number per pyramid level (csrc/swd.hip holds the rule in full).
+SWD_PATCH = 7                        # patch side
+SWD_DIM = 3 * SWD_PATCH * SWD_PATCH  # descriptor length, 147
+SWD_MAX_N = 16384                    # descriptors per set and level: both sets' fp32 keys in one workgroup's LDS
+SWD_MAX_SIDE = 128
+SWD_K_PATCH, SWD_K_DIR = 0x1234567, 0x7654321
+_SWD_TAPS = (1.0, 4.0, 6.0, 4.0, 1.0)
+
+
+def swd_default_levels(H: int, W: int) -> int:
+    """The largest L whose coarsest level has both sides >= 16 (at least 1)."""
+    L = 1
+    while H % (1 << L) == 0 and W % (1 << L) == 0 and min(H, W) >> L >= 16:
+        L += 1
+    return L
+
+
+def swd_directions(seed: int, levels: int, dirs: int, device="cpu") -> torch.Tensor:
+    """fp64 ``[levels, dirs, 147]`` unit vectors: ``normal01(seed ^ 0x7654321,
+    (l * dirs + k) * 147 + j)`` upcast and divided by its fp64 norm.  Built on
+    the CPU (one rule for both backends: the kernel takes it as a tensor)."""
+    if int(levels) < 1 or int(dirs) < 1:
+        raise ValueError(f"swd_directions: levels and dirs must be at least 1, got {levels} and {dirs}")
+    idx = torch.arange(int(levels) * int(dirs) * SWD_DIM, dtype=torch.int64)
+    g = normal01((int(seed) ^ SWD_K_DIR) & _M64, idx).double().view(int(levels), int(dirs), SWD_DIM)
+    return (g / g.square().sum(-1, keepdim=True).sqrt()).contiguous().to(device)
+
+
+def sliced_wasserstein_check(a, b, dirs, *, levels, patches, seed):
+    """Argument check shared by both backends (ValueError); returns (N, H, W, L, P, D)."""
+    name = "sliced_wasserstein"
+    for nm, x in (("a", a), ("b", b), ("dirs", dirs)):
+        if not isinstance(x, torch.Tensor):
+            raise ValueError(f"{name}: {nm} must be a tensor, got {type(x).__name__}")
+        if x.device != a.device:
+            raise ValueError(f"{name}: {nm} is on {x.device}, a on {a.device}")
+    if a.dim() != 4 or a.shape[1] != 3 or a.shape[0] < 1:
+        raise ValueError(f"{name}: a must be [N,3,H,W] with N >= 1, got {tuple(a.shape)}")
+    N, _, H, W = (int(s) for s in a.shape)
+    if isinstance(levels, bool) or not isinstance(levels, int) or levels < 1:
+        raise ValueError(f"{name}: levels must be an integer >= 1, got {levels!r}")
+    if isinstance(patches, bool) or not isinstance(patches, int) or patches < 1:
+        raise ValueError(f"{name}: patches must be an integer >= 1, got {patches!r}")
+    if not isinstance(seed, int) or isinstance(seed, bool):
+        raise ValueError(f"{name}: seed must be an integer, got {seed!r}")
+    L, P = levels, patches
+    if max(H, W) > SWD_MAX_SIDE or H % (1 << (L - 1)) or W % (1 << (L - 1)) or \
+            min(H, W) >> (L - 1) < SWD_PATCH:
+        raise ValueError(f"{name}: H and W must be at most {SWD_MAX_SIDE}, divisible by 2^(levels - 1) and at least "
+                         f"{SWD_PATCH} at the coarsest level, got {H} x {W} with levels = {L}")
+    if N * P > SWD_MAX_N:
+        raise ValueError(f"{name}: N * patches = {N * P} descriptors per set, at most {SWD_MAX_N} fit: use fewer "
+                         f"patches per image")
+    if dirs.dim() != 3 or dirs.shape[0] != L or dirs.shape[1] < 1 or dirs.shape[2] != SWD_DIM:
+        raise ValueError(f"{name}: dirs must be [{L},D,{SWD_DIM}] with D >= 1, got {tuple(dirs.shape)}")
+    for nm, x, shape, dtype in (("a", a, (N, 3, H, W), torch.float32), ("b", b, (N, 3, H, W), torch.float32),
+                                ("dirs", dirs, tuple(dirs.shape), torch.float64)):
+        if tuple(x.shape) != shape:
+            raise ValueError(f"{name}: {nm} must be {list(shape)} as a is, got {tuple(x.shape)}")
+        if x.dtype != dtype:
+            raise ValueError(f"{name}: {nm} must be {str(dtype).replace('torch.', '')}, got {x.dtype}")
+        if not x.is_contiguous():
+            raise ValueError(f"{name}: {nm} must be contiguous")
+    return N, H, W, L, P, int(dirs.shape[1])
+
+
+def _swd_blur(x: torch.Tensor, gain: float) -> torch.Tensor:
+    """The separable 5-tap [1,4,6,4,1] / 16 blur of [...,H,W] with reflect
+    borders, along W and then along H, taps ascending, times ``gain``."""
+    import torch.nn.functional as F
+    shape = x.shape
+    x = x.reshape(-1, 1, shape[-2], shape[-1])
+    d = 16.0 / math.sqrt(gain)
+    p = F.pad(x, (2, 2, 0, 0), mode="reflect")
+    s = _SWD_TAPS[0] * p[..., 0:shape[-1]]
+    for k in range(1, 5):
+        s = s + _SWD_TAPS[k] * p[..., k:k + shape[-1]]
+    p = F.pad(s / d, (0, 0, 2, 2), mode="reflect")
+    s = _SWD_TAPS[0] * p[..., 0:shape[-2], :]
+    for k in range(1, 5):
+        s = s + _SWD_TAPS[k] * p[..., k:k + shape[-2], :]
+    return (s / d).reshape(shape)
+
+
+def swd_laplacian(x: torch.Tensor, levels: int) -> list:
+    """The Laplacian pyramid of fp64 planes [...,H,W]: ``levels`` tensors, the
+    last the coarsest Gaussian level."""
+    g = [x]
+    for _ in range(levels - 1):
+        g.append(_swd_blur(g[-1], 1.0)[..., ::2, ::2])
+    out = []
+    for l in range(levels - 1):
+        z = torch.zeros_like(g[l])
+        z[..., ::2, ::2] = g[l + 1]
+        out.append(g[l] - _swd_blur(z, 4.0))
+    return out + [g[-1]]
+
+
+def swd_corners(seed: int, l: int, N: int, P: int, Hl: int, Wl: int, device="cpu"):
+    """(x0, y0) int64 [N * P] of level ``l``'s patches, image-major."""
+    q = (l * N * P + torch.arange(N * P, dtype=torch.int64, device=device))
+    s = (int(seed) ^ SWD_K_PATCH) & _M64
+    return hash_u32(s, 2 * q) % (Wl - SWD_PATCH + 1), hash_u32(s, 2 * q + 1) % (Hl - SWD_PATCH + 1)
+
+
+def sliced_wasserstein(a, b, *, dirs, levels, patches, seed, quantize=True, return_kmax=False):
+    """swd fp64 [L]: the float64 torch form of csrc/swd.hip, which states the
+    rule -- the keys are NOT rounded to fp32 here (this is the oracle; the
+    kernel's one rounding is within ``2^-23 kmax``).  ``return_kmax``: also the
+    largest ``|key|`` per level, fp64 [L]."""
+    N, H, W, L, P, D = sliced_wasserstein_check(a, b, dirs, levels=levels, patches=patches, seed=seed)
+    dev, n = a.device, N * P
+    lap = [swd_laplacian(image_map01(x, quantize), L) for x in (a, b)]
+    img = torch.arange(N, device=dev).repeat_interleave(P)[:, None, None, None]
+    ch = torch.arange(3, device=dev)[None, :, None, None]
+    ar = torch.arange(SWD_PATCH, device=dev)
+    swd = torch.zeros(L, dtype=torch.float64, device=dev)
+    kmax = torch.zeros(L, dtype=torch.float64, device=dev)
+    for l in range(L):
+        Hl, Wl = H >> l, W >> l
+        x0, y0 = swd_corners(seed, l, N, P, Hl, Wl, dev)
+        yy = (y0[:, None] + ar)[:, None, :, None]
+        xx = (x0[:, None] + ar)[:, None, None, :]
+        keys = []
+        for s in range(2):
+            v = lap[s][l][img, ch, yy, xx]                                  # [n,3,7,7]
+            mu = v.mean(dim=(0, 2, 3), keepdim=True)
+            sd = (v - mu).square().mean(dim=(0, 2, 3), keepdim=True).sqrt()
+            inv = torch.where(sd > 0, 1.0 / torch.where(sd > 0, sd, torch.ones_like(sd)), torch.zeros_like(sd))
+            keys.append(((v - mu) * inv).reshape(n, SWD_DIM) @ dirs[l].t())    # [n,D]
+        kmax[l] = torch.maximum(keys[0].abs().max(), keys[1].abs().max())
+        diff = (keys[0].sort(0).values - keys[1].sort(0).values).abs()
+        swd[l] = (diff.sum(0) / n).sum() / D
+    return (swd, kmax) if return_kmax else swd

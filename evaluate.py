@@ -31,6 +31,10 @@ weight) a voxel radiance field is fitted to the generated ``--views`` that are
 not held out and its renders are scored against the held-out generated views;
 it needs only the poses, so it works on SRN data, and with ``--procedural``
 the same score of the ground-truth images (``gt_field``) gives its ceiling.
+``--swd`` adds a distribution score that needs no trained network: the sliced
+Wasserstein distance (``ops.sliced_wasserstein``) of each guidance weight's
+generated set against the ground-truth set, one number per Laplacian-pyramid
+level, and the same between the two halves of the ground truth as its floor.
 Single process.
 """
 from __future__ import annotations
@@ -81,6 +85,15 @@ def parse(argv=None):
                     help="--field_holdout: weight of the smoothness term on the grid (colour and density alike); "
                          "not 0 fits through engine.fit_fields (profiles/field/README.md recommends a value)")
     ap.add_argument("--timesteps", type=int, default=256)
+    ap.add_argument("--swd", action="store_true",
+                    help="also score each guidance weight's generated set against the ground-truth set with the sliced "
+                         "Wasserstein distance on Laplacian-pyramid patches (ops.sliced_wasserstein): a distribution "
+                         "metric that needs no trained network; metrics.json gets an swd block.  With --samples C > 1 "
+                         "the set is sample 0 of every view")
+    ap.add_argument("--swd_patches", type=int, default=128,
+                    help="--swd: patches per image and level (capped so that images x patches <= 16384)")
+    ap.add_argument("--swd_dirs", type=int, default=512, help="--swd: projection directions per level")
+    ap.add_argument("--swd_seed", type=int, default=0, help="--swd: seed of the patch corners and the directions")
     ap.add_argument("--field_geometry", action="store_true",
                     help="--field_holdout with --procedural: also read depth, silhouette and normals out of every "
                          "fitted field at the held-out poses (ops.field_geometry) and score them against the scenes' "
@@ -113,6 +126,8 @@ def parse(argv=None):
     args = ap.parse_args(argv)
     if args.samples < 1:
         ap.error(f"--samples must be at least 1, got {args.samples}")
+    if args.swd_patches < 1 or args.swd_dirs < 1:
+        ap.error(f"--swd_patches and --swd_dirs must be at least 1, got {args.swd_patches} and {args.swd_dirs}")
     if args.field_batch < 1 or not 0.0 <= args.field_tv < float("inf"):
         ap.error(f"--field_batch must be at least 1 and --field_tv at least 0, got {args.field_batch} and "
                  f"{args.field_tv}")
@@ -228,7 +243,10 @@ def run(args) -> dict:
                                       args.autoregressive, args.seed, dev, keep_images=bool(args.field_holdout),
                                       on_view=write_pngs if args.save_png else None, solver=args.sampler,
                                       eta=args.eta, spacing=args.spacing, prediction=prediction,
-                                      consistency=args.consistency, samples=C)
+                                      consistency=args.consistency, samples=C,
+                                      swd=dict(patches=args.swd_patches, dirs=args.swd_dirs, seed=args.swd_seed)
+                                      if args.swd else None)
+    swd = rest.pop() if args.swd else None
     if dev.type == "cuda":
         torch.cuda.synchronize(dev)
     t2 = time.time()
@@ -241,6 +259,8 @@ def run(args) -> dict:
     if C > 1:
         from distributed_3d_diffusion_pytorch_amd.engine import summarize_ensemble
         result["ensemble"] = {"per_w": summarize_ensemble(rest[-1]), "rows": rest[-1]}
+    if swd is not None:
+        result["swd"] = swd
     if args.field_holdout:
         from distributed_3d_diffusion_pytorch_amd.engine import field_rows, summarize_field
         hold = [int(v) for v in args.field_holdout.split(",")]
@@ -288,6 +308,14 @@ def run(args) -> dict:
                 print(f"[evaluate] w={k}: spread co-visible {num(d['covisible']['spread'], '.3e')}  disoccluded "
                       f"{num(d['disoccluded']['spread'], '.3e')}  background "
                       f"{num(d['background']['spread'], '.3e')}", flush=True)
+    if swd is not None:
+        x1000 = lambda d: (" ".join(f"{1e3 * v:.2f}" for v in d["levels"]) +  # noqa: E731
+                           f" (mean {1e3 * d['mean']:.2f})")
+        for k, d in sorted(swd["per_w"].items(), key=lambda kv: float(kv[0])):
+            print(f"[evaluate] w={k}: SWD x 1000, fine to coarse: {x1000(d)}", flush=True)
+        if "split_floor" in swd:
+            print(f"[evaluate] SWD x 1000 between the halves of the ground truth: {x1000(swd['split_floor'])}",
+                  flush=True)
     if args.field_holdout:
         for k, d in sorted(result["field"]["per_w"].items(), key=lambda kv: float(kv[0])):
             print(f"[evaluate] w={k}: field PSNR {d['field_psnr']:.3f} dB  SSIM {d['field_ssim']:.4f} on the held-out "
