@@ -146,23 +146,24 @@ class ProceduralBatches:
 
 
 def procedural_objects(seed: int, instances: int, views: Sequence[int], imgsize: int, objects: int = 0,
-                       split: str = "val", aa: int = 3, device=None) -> List:
-    """The first ``instances`` objects of the split with the listed views, as
+                       split: str = "val", aa: int = 3, device=None, offset: int = 0) -> List:
+    """The first ``instances`` objects of the split (after skipping ``offset``
+    of them) with the listed views, as
     the ``EvalObject`` list ``engine.evaluate_objects`` and the sampler take
     (CPU fp32 tensors, names ``proc-<seed>-<id>``; ``scene`` is the object's
     fp64 table, which the geometry-aware scores read).  Rendered on ``device``
     (default: the GPU when there is one)."""
     from ..engine.evaluate import EvalObject
     n = split_size(objects, split)
-    if instances <= 0 or instances > n:
+    if instances <= 0 or offset < 0 or offset + instances > n:
         raise ValueError(f"instances must be in 1..{n} (the {split} objects among ids [0, {objects or MAX_OBJECTS})), "
-                         f"got {instances}")
+                         f"got {instances}" + (f" after {offset}" if offset else ""))
     views = [int(v) for v in views]
     if not views or min(views) < 0 or max(views) >= MAX_VIEWS:
         raise ValueError(f"views must be in [0, {MAX_VIEWS}), got {views}")
     if device is None:
         device = "cuda" if torch.cuda.is_available() else "cpu"
-    ids = [split_object(r, split) for r in range(instances)]
+    ids = [split_object(r, split) for r in range(offset, offset + instances)]
     nv = len(views)
     img, R, t, _, table = render_views(seed, [o for o in ids for _ in views], views * len(ids), imgsize, device, aa,
                                        return_table=True)

@@ -90,13 +90,15 @@ class EvalObject:
 
 
 def load_objects(root: str, index: str = "", split: str = "val", instances: int = 0, imgsize: int = 64,
-                 views: Sequence[int] = (0, 1)) -> List[EvalObject]:
+                 views: Sequence[int] = (0, 1), offset: int = 0) -> List[EvalObject]:
     """The first ``instances`` (0 = all) objects of ``split`` under the SRN
-    root -- the 90 / 10 split rule of :class:`SRNDataset` -- with the listed
-    views (positions in the object's sorted view list)."""
+    root (after skipping ``offset`` of them) -- the 90 / 10 split rule of
+    :class:`SRNDataset` -- with the listed views (positions in the object's
+    sorted view list)."""
     from ..data.srn import load_image, load_index, read_matrix, scan_index, split_ids
     idx = load_index(index) if index and os.path.exists(index) else scan_index(root)
     ids = split_ids(list(idx.keys()), split)
+    ids = ids[offset:]
     if instances:
         ids = ids[:instances]
     out = []
@@ -159,7 +161,8 @@ def evaluate_objects(model, objects: Sequence[EvalObject], input_view: int = 0, 
                      graph: Optional[bool] = None, keep_images: bool = False,
                      on_view: Optional[Callable] = None, solver: str = "ancestral", eta: float = 0.0,
                      spacing: str = "t", prediction: str = "eps", consistency: bool = False, samples: int = 1,
-                     swd: Optional[dict] = None):
+                     swd: Optional[dict] = None, knn: Optional[dict] = None, knn_train: Optional[Iterable] = None,
+                     knn_train_top: int = 4):
     """Generate ``views`` of every object from its ``input_view`` and score
     them.  Returns ``(rows, images)``: one row ``{instance, view, w, chain,
     mse, psnr, ssim}`` per (object, view, w) -- ``chain`` the global chain
@@ -211,7 +214,15 @@ def evaluate_objects(model, objects: Sequence[EvalObject], input_view: int = 0, 
     their ground truth stay on the device, and after the loop every guidance
     weight's set is scored against the ground-truth set by one
     ``ops.sliced_wasserstein`` call (:func:`swd_block`); the block is then the
-    last element of the return value."""
+    last element of the return value.
+
+    ``knn`` (a dict with ``k``) scores the same sets by precision, recall,
+    density and coverage (:func:`knn_block`); ``knn_train`` (chunks of training
+    images as :func:`nearest_train` takes them) searches every generated and
+    ground-truth image's ``knn_train_top`` nearest training images
+    (:func:`memorisation_block`).  Both go through ``ops.image_knn``.  The
+    blocks asked for are the last elements of the return value, in the order
+    swd, knn, memorisation."""
     dev = torch.device(device) if device is not None else next(model.parameters()).device
     nw, C = len(w), int(samples)
     if C < 1:
@@ -225,6 +236,8 @@ def evaluate_objects(model, objects: Sequence[EvalObject], input_view: int = 0, 
         _scenes(objects)
     swd_gen: List[List[torch.Tensor]] = [[] for _ in range(nw)]
     swd_real: List[torch.Tensor] = []
+    set_labels: List[tuple] = []                   # (instance, view) of every image of those sets
+    keep_sets = swd is not None or knn is not None or knn_train is not None
     for s in range(0, len(objects), max(int(batch), 1)):
         objs = objects[s:s + max(int(batch), 1)]
         G = len(objs)
@@ -249,10 +262,11 @@ def evaluate_objects(model, objects: Sequence[EvalObject], input_view: int = 0, 
             gt = torch.stack([o.imgs[v] for o in objs]).to(dev)
             mse, ssim = ops.image_metrics(out, gt.repeat_interleave(nc, 0), quantize=True)
             mse_l, ssim_l = mse.double().cpu().tolist(), ssim.double().cpu().tolist()
-            if swd is not None:
+            if keep_sets:
                 for i in range(nw):
                     swd_gen[i].append(out.reshape(G, nw, C, *out.shape[1:])[:, i, 0])
                 swd_real.append(gt.float())
+                set_labels.extend((o.name, int(v)) for o in objs)
             klass = None
             if consistency:
                 kept[int(v)] = out.contiguous()
@@ -310,7 +324,105 @@ def evaluate_objects(model, objects: Sequence[EvalObject], input_view: int = 0, 
     res = res + (ensemble_rows,) if C > 1 else res
     if swd is not None:
         res = res + (swd_block([torch.cat(g) for g in swd_gen], torch.cat(swd_real), w, **swd),)
+    if knn is not None:
+        res = res + (knn_block([torch.cat(g) for g in swd_gen], torch.cat(swd_real), w, **knn),)
+    if knn_train is not None:
+        res = res + (memorisation_block([torch.cat(g) for g in swd_gen], torch.cat(swd_real), w, set_labels,
+                                        knn_train, knn_train_top),)
     return res
+
+
+def knn_block(generated: Sequence[torch.Tensor], real: torch.Tensor, w: Sequence[float], k: int = 5) -> dict:
+    """Improved precision and recall (Kynkaanniemi et al. 2019) and density and
+    coverage (Naeem et al. 2020) of each guidance weight's generated set
+    ``generated[i]`` [n,3,H,W] against the ground-truth set ``real`` [n,3,H,W],
+    in 8-bit pixel space through ``ops.image_knn``: ``{k, n_images, per_w:
+    {"<w>": {precision, recall, density, coverage}}}``.  With R_X[i] the k-th
+    smallest d2 of image i inside its own set X: precision is the share of
+    generated images inside some real image's ball, density the number of real
+    balls around a generated image over k, recall the share of real images
+    inside some generated image's ball, coverage the share of real images whose
+    nearest generated image lies inside their own ball.  n >= k + 1.  With an
+    even n, ``split_floor`` is the same four numbers between the even- and the
+    odd-indexed ground-truth images: what two samples of the SAME distribution
+    score at half this set size.  Counts stay integers until the divisions."""
+    n, k = int(real.shape[0]), int(k)
+    if n < k + 1:
+        raise ValueError(f"knn: {n} images are fewer than k + 1 = {k + 1}")
+
+    def radii(x):
+        return ops.image_knn(x, x, k=k, exclude_self=True)[0][:, k - 1].contiguous()
+
+    def score(gen, ref, r_ref):
+        m, r_gen = int(ref.shape[0]), radii(gen)
+        _, _, in_ref = ops.image_knn(gen, ref, k=1, radius=r_ref)        # per generated image: the real balls it is in
+        d_near, _, in_gen = ops.image_knn(ref, gen, k=1, radius=r_gen)   # per real image: the generated balls it is in
+        return {"precision": int((in_ref > 0).sum()) / int(gen.shape[0]), "recall": int((in_gen > 0).sum()) / m,
+                "density": int(in_ref.sum()) / (k * int(gen.shape[0])),
+                "coverage": int((d_near[:, 0] <= r_ref).sum()) / m}
+
+    real = real.contiguous()
+    r_real = radii(real)
+    out = {"k": k, "n_images": n,
+           "per_w": {f"{float(wv):g}": score(g.contiguous(), real, r_real) for wv, g in zip(w, generated)}}
+    if n % 2 == 0 and n // 2 >= k + 1:
+        odd = real[1::2].contiguous()
+        out["split_floor"] = score(real[0::2].contiguous(), odd, radii(odd))
+    return out
+
+
+def nearest_train(images: torch.Tensor, chunks: Iterable, k: int = 4):
+    """The ``k`` nearest training images of every image of ``images``
+    [n,3,H,W] in 8-bit pixel space.  ``chunks`` yields ``(imgs uint8 or fp32
+    [m,3,H,W], labels)``, ``labels`` one ``(instance, view)`` per image; every
+    chunk is one ``ops.image_knn`` call on the images' device and the running
+    best k are kept by the same (d2, global index) order, so the result does
+    not depend on the chunking.  Returns ``(d2 int64 [n,k], labels)``,
+    ``labels[i][r]`` the label of image i's r-th neighbour."""
+    n, dev, k = int(images.shape[0]), images.device, int(k)
+    images = images.contiguous()
+    best_d = torch.empty(n, 0, dtype=torch.int64, device=dev)
+    best_i = torch.empty(n, 0, dtype=torch.int64, device=dev)
+    labels: list = []
+    for imgs, lab in chunks:
+        imgs = imgs.to(dev)
+        if len(lab) != imgs.shape[0]:
+            raise ValueError(f"nearest_train: a chunk of {imgs.shape[0]} images carries {len(lab)} labels")
+        d2, idx = ops.image_knn(images, imgs, k=min(k, int(imgs.shape[0])))
+        # the running list holds lower global indices and both lists ascend: a stable sort on d2 is the (d2, index) order
+        cand_d, order = torch.cat([best_d, d2], 1).sort(dim=1, stable=True)
+        best_i = torch.cat([best_i, idx + len(labels)], 1).gather(1, order[:, :k])
+        best_d = cand_d[:, :k].contiguous()
+        labels.extend(lab)
+    if best_d.shape[1] < k:
+        raise ValueError(f"nearest_train: {len(labels)} training images are fewer than k = {k}")
+    return best_d, [[labels[j] for j in row] for row in best_i.cpu().tolist()]
+
+
+def memorisation_block(generated: Sequence[torch.Tensor], real: torch.Tensor, w: Sequence[float],
+                       labels: Sequence[tuple], chunks: Iterable, top: int = 4) -> dict:
+    """The nearest training images of every generated image and of its ground
+    truth (one pass over ``chunks`` through :func:`nearest_train`), read
+    against the generated image's distance to its own ground truth.
+    ``labels[i]`` is the ``(instance, view)`` of image i of every set.  ``mse =
+    d2 / (255^2 3 H W)`` is on the [0, 1] scale of ``image_metrics``."""
+    from ..ops import torch_impl as _t
+    n, nw = int(real.shape[0]), len(generated)
+    scale = 255.0 ** 2 * real[0].numel()
+    d2, near = nearest_train(torch.cat([g.float() for g in generated] + [real.float()]), chunks, top)
+    u_real = _t.image_map_u8(real).long()
+    out = {"top": int(top), "n_images": n, "per_w": {}, "rows": []}
+    for i, wv in enumerate(w):
+        sl = slice(i * n, (i + 1) * n)
+        own = (_t.image_map_u8(generated[i]).long() - u_real).square().sum(dim=(1, 2, 3))
+        out["per_w"][f"{float(wv):g}"] = {"mse_nn_mean": float(d2[sl, 0].double().mean()) / scale,
+                                         "frac_closer_to_train": int((d2[sl, 0] < own).sum()) / n}
+        for (inst, view), dr, lr in zip(labels, d2[sl].cpu().tolist(), near[sl]):
+            out["rows"].append({"instance": inst, "view": int(view), "w": float(wv),
+                                "neighbours": [{"instance": li, "view": int(lv), "mse": d / scale}
+                                               for d, (li, lv) in zip(dr, lr)]})
+    out["gt_mse_nn_mean"] = float(d2[nw * n:, 0].double().mean()) / scale
+    return out
 
 
 def swd_block(generated: Sequence[torch.Tensor], real: torch.Tensor, w: Sequence[float], patches: int = 128,

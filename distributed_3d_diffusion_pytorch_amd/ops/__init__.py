@@ -510,6 +510,29 @@ def sliced_wasserstein(a, b, *, levels=None, patches: int = 128, dirs=512, seed:
     return impl.sliced_wasserstein(a, b, dirs=dirs, levels=levels, patches=patches, seed=seed, quantize=quantize)
 
 
+def image_knn(a, b, *, k: int, exclude_self: bool = False, radius=None):
+    """Exact k-nearest-neighbour search between two image sets in 8-bit pixel
+    space, without an N x M distance matrix: the primitive under improved
+    precision / recall, density / coverage and the nearest-training-image
+    check.  ``a`` ``[N,3,H,W]`` (queries) and ``b`` ``[M,3,H,W]`` (candidates)
+    are each fp32 in [-1, 1], mapped to the byte ``save_png`` writes as
+    ``image_metrics(quantize=True)`` maps it, or ``torch.uint8``, taken as it
+    is.  Returns ``(d2, idx)`` int64 ``[N,k]``: per query the k smallest
+    ``d2(i, j) = sum_p (u_a[i,p] - u_b[j,p])^2`` -- an exact integer in units
+    of (1/255)^2 -- ascending, and the matching j; the order is the total order
+    on ``(d2, j)``, so equal distances go to the lower index and the result
+    does not depend on how the work was split.  ``exclude_self`` skips j == i
+    (``b`` is ``a``).  ``radius`` int64 ``[M]`` (a squared radius per candidate,
+    -1 = never inside) adds a third result ``inside`` int64 ``[N]``:
+    ``#{j : d2(i, j) <= radius[j]}`` over all M candidates.  1 <= k <= 8, k <=
+    M (M - 1 with ``exclude_self``), ``3 H W <= 131071``, else ValueError.  HIP
+    on the int8 matrix units (``csrc/knn.hip``, which states the rule) on the
+    GPU, the exact torch form on the CPU; both give the same bits."""
+    _t.image_knn_check(a, b, k=k, exclude_self=exclude_self, radius=radius)
+    impl = _h() if a.is_cuda and use_hip(a, any_dtype=True) else _t
+    return impl.image_knn(a, b, k=k, exclude_self=exclude_self, radius=radius)
+
+
 def psnr(mse):
     """``10 log10(1 / mse)`` on the [0, 1] scale; ``+inf`` where ``mse == 0``."""
     return -10.0 * torch.log10(torch.as_tensor(mse, dtype=torch.float32))
@@ -521,7 +544,7 @@ posenc_nerf = _t.posenc_nerf
 
 __all__ = ["diffusion_inputs", "diff_loss_nhwc", "diff_loss_rows", "loss_bins_add", "group_norm", "gn_film", "conv3x3", "linear", "film_batch", "cat_gn_silu_dense", "cond_conv", "ray_posenc_dir",
            "ray_origin_pe", "ray_conditioning", "attention", "avgpool2", "upsample2",
-           "silu", "logsnr_mlp", "ray_posenc", "image_metrics", "scene_render", "procedural_render", "procedural_batch", "view_consistency", "ensemble_stats", "field_render", "field_loss_grad", "field_batch_loss_grad", "field_adam_tv", "field_geometry", "depth_consistency", "sliced_wasserstein", "psnr", "posenc_ddpm", "camera_rays", "posenc_nerf", "set_backend",
+           "silu", "logsnr_mlp", "ray_posenc", "image_metrics", "scene_render", "procedural_render", "procedural_batch", "view_consistency", "ensemble_stats", "field_render", "field_loss_grad", "field_batch_loss_grad", "field_adam_tv", "field_geometry", "depth_consistency", "sliced_wasserstein", "image_knn", "psnr", "posenc_ddpm", "camera_rays", "posenc_nerf", "set_backend",
            "use_hip", "load_library", "library_error", "lib_path"]
 
 

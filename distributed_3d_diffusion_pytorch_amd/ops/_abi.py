@@ -155,6 +155,10 @@ SIGNATURES = {
     # swd.hip
     "d3d_swd_cfg": [I],
     "d3d_sliced_wasserstein": [P, P, P, L, I, I, I, I, I, U64, I, P, P, P, P, P],
+    # knn.hip
+    "d3d_knn_rows": [L],
+    "d3d_knn_splits": [L, L, I],
+    "d3d_image_knn": [P, I, P, I, L, L, L, I, I, P, I, P, P, P, P, P, P, P, P, P, P],
 }
 
 
@@ -167,4 +171,4 @@ def declare(lib: C.CDLL) -> None:
         fn.restype = C.c_long if name in RET_LONG else C.c_int
 
 
-RET_LONG = {"d3d_mlp_ws", "d3d_wgrad_group"}
+RET_LONG = {"d3d_mlp_ws", "d3d_wgrad_group", "d3d_knn_rows"}

@@ -3180,3 +3180,38 @@ def sliced_wasserstein(a, b, *, dirs, levels, patches, seed, quantize=True):
                                      lap.data_ptr(), stat.data_ptr(), part.data_ptr(), swd.data_ptr(), _st()),
          "sliced_wasserstein")
     return swd
+
+
+# ------------------------------------------------- exact image k-NN (int8 MFMA) ---
+def image_knn(a, b, *, k, exclude_self=False, radius=None, splits=0):
+    """(d2 [N,k], idx [N,k][, inside [N]]) int64 of the k nearest images of
+    ``b`` [M,3,H,W] to every image of ``a`` [N,3,H,W] in 8-bit pixel space
+    (csrc/knn.hip, which states the rule: both sets packed to int8 panels, a
+    tile product on ``v_mfma_i32_16x16x64_i8`` over splits of M with each
+    lane's running top-k in registers, then a merge of the splits; exactly the
+    numbers of ``torch_impl.image_knn``).  ``splits`` > 0: at most that many
+    splits of M instead of the launcher's own count (the result does not depend
+    on it).  Graph-capturable."""
+    N, M, D = _t.image_knn_check(a, b, k=k, exclude_self=exclude_self, radius=radius)
+    dev = a.device
+    same = b is a
+    a = a.contiguous()
+    b = a if same else b.contiguous()
+    Dp = (D + 127) // 128 * 128
+    ra, rb = _lib.d3d_knn_rows(N), _lib.d3d_knn_rows(M)
+    pa = torch.empty(ra * Dp, dtype=torch.int8, device=dev)
+    na = torch.empty(ra, dtype=torch.int32, device=dev)
+    pb = None if same else torch.empty(rb * Dp, dtype=torch.int8, device=dev)
+    nb = None if same else torch.empty(rb, dtype=torch.int32, device=dev)
+    S = _lib.d3d_knn_splits(N, M, int(splits))
+    keys = torch.empty(S, N, k, dtype=torch.int64, device=dev)
+    cnt = None if radius is None else torch.empty(S, N, dtype=torch.int64, device=dev)
+    d2 = torch.empty(N, k, dtype=torch.int64, device=dev)
+    idx = torch.empty(N, k, dtype=torch.int64, device=dev)
+    inside = None if radius is None else torch.empty(N, dtype=torch.int64, device=dev)
+    rad = None if radius is None else radius.contiguous()
+    _chk(_lib.d3d_image_knn(a.data_ptr(), int(a.dtype == torch.uint8), b.data_ptr(), int(b.dtype == torch.uint8),
+                            N, M, D, int(k), int(bool(exclude_self)), _ptr(rad), int(splits), pa.data_ptr(),
+                            na.data_ptr(), _ptr(pb), _ptr(nb), keys.data_ptr(), _ptr(cnt), d2.data_ptr(),
+                            idx.data_ptr(), _ptr(inside), _st()), "image_knn")
+    return (d2, idx) if radius is None else (d2, idx, inside)

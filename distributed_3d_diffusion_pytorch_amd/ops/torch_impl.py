@@ -459,10 +459,9 @@ def ssim_window() -> list:
 def image_map01(x: torch.Tensor, quantize: bool) -> torch.Tensor:
     """[-1, 1] fp32 -> [0, 1] float64; ``quantize``: through the uint8 value
     ``sampling.py:save_png`` writes (fp32 add, fp32 multiply, truncation)."""
-    c = x.float().clamp(-1.0, 1.0)
     if quantize:
-        return ((c + 1.0) * 127.5).to(torch.uint8).double() / 255.0
-    return (c.double() + 1.0) * 0.5
+        return image_map_u8(x).double() / 255.0
+    return (x.float().clamp(-1.0, 1.0).double() + 1.0) * 0.5
 
 
 def image_metrics(pred: torch.Tensor, target: torch.Tensor, quantize: bool = True):
@@ -1687,3 +1686,75 @@ def sliced_wasserstein(a, b, *, dirs, levels, patches, seed, quantize=True, retu
         diff = (keys[0].sort(0).values - keys[1].sort(0).values).abs()
         swd[l] = (diff.sum(0) / n).sum() / D
     return (swd, kmax) if return_kmax else swd
+
+
+# ------------------------------------------------------- exact image k-NN ---
+KNN_MAX_K = 8
+KNN_MAX_D = 131071                   # D 2^14 < 2^31: the kernel's int32 accumulators and row norms cannot overflow
+
+
+def image_map_u8(x: torch.Tensor) -> torch.Tensor:
+    """[-1, 1] fp32 -> the uint8 value ``sampling.py:save_png`` writes (fp32
+    add, fp32 multiply, truncation): the integer form of ``image_map01``."""
+    return ((x.float().clamp(-1.0, 1.0) + 1.0) * 127.5).to(torch.uint8)
+
+
+def image_knn_check(a, b, *, k, exclude_self, radius):
+    """Argument check shared by both backends (ValueError); returns (N, M, D)."""
+    name = "image_knn"
+    for nm, x in (("a", a), ("b", b)):
+        if not isinstance(x, torch.Tensor):
+            raise ValueError(f"{name}: {nm} must be a tensor, got {type(x).__name__}")
+        if x.dim() != 4 or x.shape[1] != 3 or min(x.shape) < 1:
+            raise ValueError(f"{name}: {nm} must be a non-empty [n,3,H,W] tensor, got {tuple(x.shape)}")
+        if x.dtype not in (torch.float32, torch.uint8):
+            raise ValueError(f"{name}: {nm} must be float32 in [-1, 1] or uint8, got {x.dtype}")
+    if b.device != a.device or a.shape[1:] != b.shape[1:]:
+        raise ValueError(f"{name}: a and b must share a device and [3,H,W], got {tuple(a.shape)} on {a.device} and "
+                         f"{tuple(b.shape)} on {b.device}")
+    N, M, D = int(a.shape[0]), int(b.shape[0]), int(a.shape[1] * a.shape[2] * a.shape[3])
+    if D > KNN_MAX_D:
+        raise ValueError(f"{name}: 3 H W = {D} is above {KNN_MAX_D}, the limit of the exact int32 accumulation")
+    if isinstance(k, bool) or not isinstance(k, int) or not 1 <= k <= KNN_MAX_K:
+        raise ValueError(f"{name}: k must be an integer in 1 .. {KNN_MAX_K}, got {k!r}")
+    if k > M - (1 if exclude_self else 0):
+        raise ValueError(f"{name}: k = {k} neighbours among {M} candidates" + (" without self" if exclude_self else ""))
+    if radius is not None:
+        if not isinstance(radius, torch.Tensor) or radius.dtype != torch.int64 or tuple(radius.shape) != (M,) \
+                or radius.device != a.device:
+            raise ValueError(f"{name}: radius must be an int64 [{M}] tensor on {a.device}")
+    return N, M, D
+
+
+def image_knn(a, b, *, k, exclude_self=False, radius=None, chunk=2048):
+    """(d2 [N,k], idx [N,k][, inside [N]]) int64: the torch form of
+    csrc/knn.hip, which states the rule.  The distances are exact integers:
+    the shifted bytes ``u - 128`` are multiplied in float64, where every
+    partial sum is an integer below 2^53, over chunks of ``b``; the running
+    best k and the chunk are ranked by a stable sort on d2 with the lower
+    indices first, which is the total order on (d2, j)."""
+    N, M, D = image_knn_check(a, b, k=k, exclude_self=exclude_self, radius=radius)
+    dev = a.device
+
+    def shifted(x):
+        u = x if x.dtype == torch.uint8 else image_map_u8(x)
+        return u.reshape(x.shape[0], D).double() - 128.0
+
+    sa = shifted(a)
+    na = (sa * sa).sum(1).long()
+    rows = torch.arange(N, device=dev)[:, None]
+    best_d = torch.empty(N, 0, dtype=torch.int64, device=dev)
+    best_i = torch.empty(N, 0, dtype=torch.int64, device=dev)
+    inside = torch.zeros(N, dtype=torch.int64, device=dev)
+    for j0 in range(0, M, chunk):
+        sb = shifted(b[j0:j0 + chunk])
+        j = torch.arange(j0, j0 + sb.shape[0], device=dev)[None, :]
+        d2 = na[:, None] + (sb * sb).sum(1).long()[None, :] - 2 * (sa @ sb.t()).long()
+        skip = (j == rows) if exclude_self else torch.zeros_like(d2, dtype=torch.bool)
+        if radius is not None:
+            inside += ((d2 <= radius[j0:j0 + sb.shape[0]][None, :]) & ~skip).sum(1)
+        cand_d = torch.cat([best_d, d2.masked_fill(skip, 1 << 62)], 1)
+        cand_i = torch.cat([best_i, j.expand(N, -1)], 1)
+        cand_d, order = cand_d.sort(dim=1, stable=True)
+        best_d, best_i = cand_d[:, :k].contiguous(), cand_i.gather(1, order[:, :k])
+    return (best_d, best_i) if radius is None else (best_d, best_i, inside)

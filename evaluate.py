@@ -35,6 +35,12 @@ the same score of the ground-truth images (``gt_field``) gives its ceiling.
 Wasserstein distance (``ops.sliced_wasserstein``) of each guidance weight's
 generated set against the ground-truth set, one number per Laplacian-pyramid
 level, and the same between the two halves of the ground truth as its floor.
+``--knn`` separates fidelity from diversity: precision, recall, density and
+coverage of each generated set against the ground-truth set from exact nearest
+neighbours in 8-bit pixel space (``ops.image_knn``); ``--knn_train N`` searches
+the nearest images of the first N training objects for every generated image:
+one that is closer to a training image than to its own ground truth is
+regurgitated.
 Single process.
 """
 from __future__ import annotations
@@ -94,6 +100,17 @@ def parse(argv=None):
                     help="--swd: patches per image and level (capped so that images x patches <= 16384)")
     ap.add_argument("--swd_dirs", type=int, default=512, help="--swd: projection directions per level")
     ap.add_argument("--swd_seed", type=int, default=0, help="--swd: seed of the patch corners and the directions")
+    ap.add_argument("--knn", action="store_true",
+                    help="also score each guidance weight's generated set against the ground-truth set by improved "
+                         "precision / recall and density / coverage from exact k-nearest neighbours in 8-bit pixel "
+                         "space (ops.image_knn); metrics.json gets a knn block.  With --samples C > 1 the set is "
+                         "sample 0 of every view")
+    ap.add_argument("--knn_k", type=int, default=5, help="--knn: the neighbour that sets an image's radius (1..8)")
+    ap.add_argument("--knn_train", type=int, default=0,
+                    help="search the nearest training images (the input view and --views of the first N objects of "
+                         "the train split, 0 = off) of every generated and ground-truth image; metrics.json gets a "
+                         "memorisation block")
+    ap.add_argument("--knn_train_top", type=int, default=4, help="--knn_train: neighbours kept per image (1..8)")
     ap.add_argument("--field_geometry", action="store_true",
                     help="--field_holdout with --procedural: also read depth, silhouette and normals out of every "
                          "fitted field at the held-out poses (ops.field_geometry) and score them against the scenes' "
@@ -128,6 +145,9 @@ def parse(argv=None):
         ap.error(f"--samples must be at least 1, got {args.samples}")
     if args.swd_patches < 1 or args.swd_dirs < 1:
         ap.error(f"--swd_patches and --swd_dirs must be at least 1, got {args.swd_patches} and {args.swd_dirs}")
+    if not 1 <= args.knn_k <= 8 or not 1 <= args.knn_train_top <= 8 or args.knn_train < 0:
+        ap.error(f"--knn_k and --knn_train_top must be in 1..8 and --knn_train at least 0, got {args.knn_k}, "
+                 f"{args.knn_train_top} and {args.knn_train}")
     if args.field_batch < 1 or not 0.0 <= args.field_tv < float("inf"):
         ap.error(f"--field_batch must be at least 1 and --field_tv at least 0, got {args.field_batch} and "
                  f"{args.field_tv}")
@@ -172,6 +192,28 @@ def val_loss(model, cfg, args, dev, prediction: str):
     table = torch.zeros(args.loss_bins, 5, dtype=torch.float64, device=dev) if args.loss_bins > 0 else None
     loss = float(heldout_loss(model, batches, args.seed, dc, model.compute_dtype, bins=table))
     return loss, (loss_bins_report(table, dc.logsnr_min, dc.logsnr_max) if table is not None else None)
+
+
+def train_chunks(args, views, dev, objects_per_chunk: int = 64):
+    """The images of the first ``--knn_train`` objects of the train split at
+    ``views`` as ``engine.nearest_train`` takes them: ``(uint8 [m,3,H,W] on
+    ``dev``, [(instance, view)] * m)`` for at most ``objects_per_chunk``
+    objects at a time, so a large N never sits on the device at once."""
+    from distributed_3d_diffusion_pytorch_amd.ops.torch_impl import image_map_u8
+    import torch
+    for s in range(0, args.knn_train, objects_per_chunk):
+        m = min(objects_per_chunk, args.knn_train - s)
+        if args.procedural:
+            from distributed_3d_diffusion_pytorch_amd.data import procedural_objects
+            objs = procedural_objects(args.proc_seed, m, views, args.imgsize, objects=args.proc_objects, split="train",
+                                      device=dev, offset=s)
+        else:
+            from distributed_3d_diffusion_pytorch_amd.engine import load_objects
+            objs = load_objects(args.data, args.index, "train", m, args.imgsize, views, offset=s)
+        if not objs:
+            return
+        yield (image_map_u8(torch.stack([o.imgs[v] for o in objs for v in views])).to(dev),
+               [(o.name, v) for o in objs for v in views])
 
 
 def run(args) -> dict:
@@ -245,7 +287,11 @@ def run(args) -> dict:
                                       eta=args.eta, spacing=args.spacing, prediction=prediction,
                                       consistency=args.consistency, samples=C,
                                       swd=dict(patches=args.swd_patches, dirs=args.swd_dirs, seed=args.swd_seed)
-                                      if args.swd else None)
+                                      if args.swd else None, knn=dict(k=args.knn_k) if args.knn else None,
+                                      knn_train=train_chunks(args, sorted({args.input_view, *views}), dev)
+                                      if args.knn_train else None, knn_train_top=args.knn_train_top)
+    memorisation = rest.pop() if args.knn_train else None
+    knn = rest.pop() if args.knn else None
     swd = rest.pop() if args.swd else None
     if dev.type == "cuda":
         torch.cuda.synchronize(dev)
@@ -261,6 +307,10 @@ def run(args) -> dict:
         result["ensemble"] = {"per_w": summarize_ensemble(rest[-1]), "rows": rest[-1]}
     if swd is not None:
         result["swd"] = swd
+    if knn is not None:
+        result["knn"] = knn
+    if memorisation is not None:
+        result["memorisation"] = memorisation
     if args.field_holdout:
         from distributed_3d_diffusion_pytorch_amd.engine import field_rows, summarize_field
         hold = [int(v) for v in args.field_holdout.split(",")]
@@ -316,6 +366,18 @@ def run(args) -> dict:
         if "split_floor" in swd:
             print(f"[evaluate] SWD x 1000 between the halves of the ground truth: {x1000(swd['split_floor'])}",
                   flush=True)
+    if knn is not None:
+        four = lambda d: (f"precision {d['precision']:.3f}  recall {d['recall']:.3f}  density "  # noqa: E731
+                          f"{d['density']:.3f}  coverage {d['coverage']:.3f}")
+        for k, d in sorted(knn["per_w"].items(), key=lambda kv: float(kv[0])):
+            print(f"[evaluate] w={k}: k={knn['k']} pixel-space {four(d)}", flush=True)
+        if "split_floor" in knn:
+            print(f"[evaluate] between the halves of the ground truth: {four(knn['split_floor'])}", flush=True)
+    if memorisation is not None:
+        for k, d in sorted(memorisation["per_w"].items(), key=lambda kv: float(kv[0])):
+            print(f"[evaluate] w={k}: nearest training image at mse {d['mse_nn_mean']:.3e} (ground truth's: "
+                  f"{memorisation['gt_mse_nn_mean']:.3e}); {100 * d['frac_closer_to_train']:.1f}% closer to a "
+                  f"training image than to their own ground truth", flush=True)
     if args.field_holdout:
         for k, d in sorted(result["field"]["per_w"].items(), key=lambda kv: float(kv[0])):
             print(f"[evaluate] w={k}: field PSNR {d['field_psnr']:.3f} dB  SSIM {d['field_ssim']:.4f} on the held-out "
